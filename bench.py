@@ -10,7 +10,12 @@ over the fixed dataset) and the int16 match graph is all-gathered by the
 C-ABI's RCCL collective (``sfmhip_allgather``), chunk by chunk, overlapped with
 the match launches.
 
-Secondary lines (``secondary`` list of the same JSON object):
+A plain run (``bench.py --gpus N --steps K --warmup W``) does only that: it sets
+up, warms up, times the K steps, writes the last step's outputs with
+``--dump-outputs DIR`` and prints the result line.  Everything below runs only
+with ``--full``.
+
+Secondary lines (``--full``; ``secondary`` list of the same JSON object):
   * TSDF Mvoxel/sec (C5), z-slab sharded over ranks;
   * BA obs/sec: DLT + residual + FD Jacobian (C3 BA workload), DLT and FD-J
     kernels timed apart, with the numpy/scipy CPU baseline;
@@ -18,10 +23,12 @@ Secondary lines (``secondary`` list of the same JSON object):
     the north-star composite (C3 match + C3 DLT/BA evaluation + C5 TSDF vs the
     summed CPU wall-clock), DDA traversal, plenoxel render, vq, geometric
     verification, PnP and the plenoxel training step.
-CPU baselines follow BASELINE.md §2: 1 warm-up + median of 3 timed runs, with
-every host thread the box gives us and again with 1 thread (``value_1thread``).
+CPU baselines (``--full``) follow BASELINE.md §2: 1 warm-up + median of 3 timed
+runs, with every host thread the box gives us and again with 1 thread
+(``value_1thread``).
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline]
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+        python bench.py --full [--steps K] [--warmup W] [--no-cpu-baseline] [--skip-secondary]
         python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -1200,6 +1207,29 @@ def launch_ranks(n: int, argv) -> int:
     return rc
 
 
+DUMP_ROWS = 2048              # pair rows of the match graph kept by --dump-outputs (x 4096 f32 = 32 MiB)
+
+
+def dump_outputs(dirname: str, graph: torch.Tensor) -> dict:
+    """--dump-outputs: the match graph the last timed step returned (what a caller of
+    ``dist.match_all_pairs_sharded`` receives: (P, m_pad) matches0, -1 = no match), as
+    float32 .npy files.  The C3 graph is 135 M entries, so the dump keeps a fixed,
+    seeded sample of its pair rows (all rows while P <= DUMP_ROWS), the rows' indices
+    and, over every row, the number of matches of each pair."""
+    os.makedirs(dirname, exist_ok=True)
+    P = int(graph.shape[0])
+    if P > DUMP_ROWS:
+        rows = np.sort(np.random.default_rng(0).choice(P, DUMP_ROWS, replace=False))
+    else:
+        rows = np.arange(P)
+    sample = graph[torch.from_numpy(rows).to(graph.device)].to(torch.float32).cpu().numpy()
+    counts = (graph >= 0).sum(dim=1).to(torch.float32).cpu().numpy()
+    files = {"matches0_rows": sample, "matches0_row_index": rows.astype(np.float64), "matches_per_pair": counts}
+    for name, a in files.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in files.items()}
+
+
 def dry_run(world: int, rank: int, backend: str) -> dict:
     """--dry-run: the rank/world plumbing without any GPU work (CPU tests of
     the launcher): every rank joins the process group and the world is
@@ -1221,8 +1251,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--skip-secondary", action="store_true")
+    ap.add_argument("--full", action="store_true", default=os.environ.get("SFMHIP_BENCH_FULL", "") not in ("", "0"),
+                    help="also run the secondary lines, the CPU baselines and the composite (default: the "
+                         "headline's set-up, warm-up and timed steps only); SFMHIP_BENCH_FULL=1 in the "
+                         "environment does the same, for the session scripts under tools/")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32/float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baselines")
+    ap.add_argument("--skip-secondary", action="store_true", help="with --full: leave out the secondary lines")
     ap.add_argument("--no-rebalance", action="store_true",
                     help="N > 1: keep equal-thickness TSDF slabs (default: re-cut from measured fusion times)")
     ap.add_argument("--rebalance-rounds", type=int, default=3)
@@ -1235,6 +1271,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit(f"--gpus must be >= 1 (got {args.gpus})")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit(f"--steps must be >= 1 and --warmup >= 0 (got {args.steps}, {args.warmup})")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         # one process per GPU: this process only launches and waits (no GPU call here)
@@ -1272,7 +1310,7 @@ def main():
     sfm = importlib.import_module("3d_reconstruction_amd")
     syn = importlib.import_module("3d_reconstruction_amd.synthetic")
     sdist = importlib.import_module("3d_reconstruction_amd.dist")
-    cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
 
     # the match-graph collective: the C-ABI's RCCL communicator (sfmhip_comm_*),
     # bootstrapped over the torch.distributed group; gloo rehearsals use torch
@@ -1316,10 +1354,11 @@ def main():
     ops_per_launch = 2.0 * M_KPT * M_KPT * DIM * pairs_per_launch
     achieved_tops = ops_per_launch / (kern_ms * 1e-3) / 1e12
     graph = holder["g"]
-    n_matched = int((graph >= 0).sum().item())
     rescored = int(bank.last_resolved.item()) if bank.last_resolved is not None else None
-    log(f"[rank {rank}] match: {ms_per_step:.2f} ms/step, kernel {kern_ms:.2f} ms, "
-        f"{achieved_tops:.0f} TOPS, {n_matched} matches in the gathered graph {tuple(graph.shape)} {graph.dtype}")
+    log(f"[rank {rank}] match: {ms_per_step:.2f} ms/step, kernel {kern_ms:.2f} ms, {achieved_tops:.0f} TOPS, "
+        f"gathered graph {tuple(graph.shape)} {graph.dtype}"
+        + (f", {int((graph >= 0).sum().item())} matches" if args.full else ""))
+    dumped = dump_outputs(args.dump_outputs, graph) if (args.dump_outputs and rank == 0) else None
 
     result = {
         "metric": "image-pairs matched/sec",
@@ -1351,11 +1390,13 @@ def main():
                      "algorithmic": "2*M*N*d int8 ops per pair x pairs per launch (the f64 re-score of the "
                                     "uncertified rows is overhead, not work)"},
     }
+    if dumped is not None:
+        result["dumped_outputs"] = dumped
     match_cpu = None
     del bank, holder["g"], graph
     torch.cuda.empty_cache()
 
-    if not args.skip_secondary:
+    if args.full and not args.skip_secondary:
         # ---------------- C5: TSDF ------------------------------------------
         t0 = time.perf_counter()
         depth, poses, K = syn.tsdf_scene(TSDF_F, syn.IMG_H, syn.IMG_W, device=device)

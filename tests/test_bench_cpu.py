@@ -116,6 +116,42 @@ def test_bench_single_rank_default():
     assert lines[0]["n_gpus"] == 1
 
 
+def test_bench_accepts_full_and_dump_outputs(tmp_path):
+    """--full and --dump-outputs are options of the benchmark; a dry run writes nothing."""
+    p, lines = _run_bench(["--full", "--dump-outputs", str(tmp_path / "d"), "--dry-run"])
+    assert p.returncode == 0, p.stderr
+    assert lines[0]["n_gpus"] == 1
+    assert not (tmp_path / "d").exists()
+    p, lines = _run_bench(["--steps", "0", "--dry-run"])
+    assert p.returncode != 0 and not lines
+
+
+def test_dump_outputs_is_a_fixed_float_sample(tmp_path):
+    """The dump of a match graph larger than DUMP_ROWS rows: float32 arrays, the same seeded
+    rows on every call, each dumped row equal to the graph's, counts over every row."""
+    import torch
+    g = torch.Generator().manual_seed(3)
+    P, m = bench.DUMP_ROWS + 1000, 24
+    graph = torch.randint(-1, m, (P, m), generator=g, dtype=torch.int16)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), graph)
+    bench.dump_outputs(str(tmp_path / "b"), graph)
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in shapes}
+    b = {n: np.load(tmp_path / "b" / (n + ".npy")) for n in shapes}
+    assert sorted(a) == ["matches0_row_index", "matches0_rows", "matches_per_pair"]
+    for n in a:
+        assert a[n].dtype in (np.float32, np.float64) and list(a[n].shape) == shapes[n]
+        np.testing.assert_array_equal(a[n], b[n])
+    rows = a["matches0_row_index"].astype(np.int64)
+    assert rows.shape == (bench.DUMP_ROWS,) and len(set(rows.tolist())) == bench.DUMP_ROWS
+    np.testing.assert_array_equal(a["matches0_rows"], graph.numpy()[rows].astype(np.float32))
+    np.testing.assert_array_equal(a["matches_per_pair"], (graph.numpy() >= 0).sum(1).astype(np.float32))
+    # the C3 dump (DUMP_ROWS x 4096 f32 + 32,896 counts + the indices) stays under 64 MB
+    assert bench.DUMP_ROWS * bench.M_KPT * 4 + bench.N_IMG * (bench.N_IMG - 1) // 2 * 4 + bench.DUMP_ROWS * 8 < 64e6
+    # a graph of at most DUMP_ROWS rows is dumped whole
+    small = bench.dump_outputs(str(tmp_path / "c"), graph[:10])
+    assert small["matches0_rows"] == [10, m]
+
+
 def test_bench_launcher_propagates_rank_failure():
     p, lines = _run_bench(["--gpus", "2", "--dist-backend", "no_such_backend", "--dry-run"])
     assert p.returncode != 0 and not lines

@@ -205,7 +205,7 @@ def test_tsdf_oracle_order_free_vs_sequential():
 def test_bow_oracle_matches_reference():
     from oracle import bow as ob
     g = golden("bow_golden.npz")
-    desc = list(g["desc"])
+    desc = list(golden("bow_desc_golden.npz")["desc"])      # the descriptors live in a file of their own (size)
     assert np.array_equal(ob.stack_descriptors(desc).sum(1), g["stacked_rowsum"])   # bow.py:14-18 order
     book, dist = ob.codebook(desc, 200, 1, seed=123)
     assert np.array_equal(book, g["codebook"]) and dist == float(g["variance"])

@@ -2,6 +2,7 @@
 # kernel-trace profile of the same bench.  Every GPU step has its own time
 # limit and the chain stops at the first failure.
 set -o pipefail
+export SFMHIP_BENCH_FULL=1   # every bench.py run below is a --full run (secondary lines + CPU baselines)
 cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
 TAG=${TAG:-r1}

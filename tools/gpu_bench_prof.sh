@@ -1,6 +1,7 @@
 # Bench line + rocprofv3 kernel-trace stats of the same bench, then the N>1
 # path rehearsals (one-rank C-ABI RCCL comm; 2-rank gloo on one GPU).
 set -o pipefail
+export SFMHIP_BENCH_FULL=1   # every bench.py run below is a --full run (secondary lines + CPU baselines)
 cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
 TAG=${TAG:-r2}

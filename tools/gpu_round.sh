@@ -2,6 +2,7 @@
 # the bench, PMC traffic passes for the match + TSDF kernels, and a 2-rank
 # rehearsal of the distributed bench path (gloo, both ranks on device 0).
 set -o pipefail
+export SFMHIP_BENCH_FULL=1   # every bench.py run below is a --full run (secondary lines + CPU baselines)
 cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
 TAG=${TAG:-r1}

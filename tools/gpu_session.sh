@@ -7,6 +7,7 @@
 #   EXTRA="cmd"  one more command (own time limit 300 s)
 # Every GPU step has its own time limit; the chain stops at the first failure.
 set -o pipefail
+export SFMHIP_BENCH_FULL=1   # every bench.py run below is a --full run (secondary lines + CPU baselines)
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 mkdir -p gpurun_out
 TAG=${TAG:-s}
