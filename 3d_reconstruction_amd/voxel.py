@@ -13,6 +13,8 @@
   are discarded by the reference at 251-252) + ``SDFGrid.forward``.
 * :func:`tsdf_integrate` — TSDF fusion of depth maps into a (D,H,W) grid laid
   out like the ``sdf.py`` grid (build-defined).
+* :func:`tsdf_extract_surface` — the fused grid's iso-surface as a triangle mesh
+  (marching tetrahedra, build-defined; ``mesh.write_ply`` stores it).
 """
 from __future__ import annotations
 
@@ -339,3 +341,59 @@ def tsdf_cull_stats(shape, depth: torch.Tensor, poses: torch.Tensor, K: torch.Te
     n = max(int(st[0]), 1)
     return {"tested": int(st[0]), "culled": int(st[1]), "free": int(st[2]),
             "culled_frac": st[1] / n, "free_frac": st[2] / n, "full_frac": 1 - (st[1] + st[2]) / n}
+
+
+def tsdf_extract_surface(T: torch.Tensor, Wt: torch.Tensor, bmin, bmax, iso: float = 0.0, min_weight: float = 1.0,
+                         z0: int = 0, z1: int | None = None, normals: bool = True):
+    """Triangle mesh of the iso-surface of a fused TSDF grid (marching tetrahedra on the
+    Kuhn 6-tetrahedron split; the semantics are the V6 block of include/sfmhip.h).
+
+    T, Wt: (D,H,W) contiguous f32 device tensors as :func:`tsdf_integrate` leaves them;
+    a voxel counts as observed when ``Wt >= min_weight`` and T is finite, and only cells
+    whose 8 corners are observed emit triangles.  [z0, z1) is a range of cell layers
+    (default: all D-1); the triangle soups of a partition into ranges concatenate to the
+    whole call's soup bit for bit (multi-GPU z-slabs).
+
+    Returns device tensors ``(vertices (V,3) f32, normals (V,3) f32 | None, faces (F,3)
+    int32)``: a consistently oriented mesh, normals and face orientation towards free
+    space (increasing T).  D, H or W of 1, or z0 == z1, gives empty (0,3) outputs."""
+    gpu = require_gpu()
+    if not isinstance(T, torch.Tensor) or not isinstance(Wt, torch.Tensor):
+        raise ValueError("T and Wt must be torch tensors")
+    if T.dtype != torch.float32 or Wt.dtype != torch.float32 or not T.is_contiguous() or not Wt.is_contiguous():
+        raise ValueError("T and Wt must be contiguous float32 device tensors")
+    if T.dim() != 3 or tuple(Wt.shape) != tuple(T.shape):
+        raise ValueError(f"T and Wt must be (D,H,W) tensors of one shape, got {tuple(T.shape)} and "
+                         f"{tuple(Wt.shape)}")
+    if T.device != gpu or Wt.device != gpu:
+        raise ValueError(f"T and Wt must live on the current HIP device {gpu}, got {T.device} / {Wt.device}")
+    D, H, W = T.shape
+    if min(D, H, W) < 1:
+        raise ValueError(f"empty grid {tuple(T.shape)}")
+    z0 = int(z0)
+    z1 = D - 1 if z1 is None else int(z1)
+    if not 0 <= z0 <= z1 <= D - 1:
+        raise ValueError(f"cell-layer range [{z0}, {z1}) outside [0, {D - 1}]")
+    if not float(min_weight) > 0.0:
+        raise ValueError(f"min_weight must be > 0, got {min_weight}")
+    for name, b in (("bmin", bmin), ("bmax", bmax)):
+        if np.size(b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else b) not in (1, 3):
+            raise ValueError(f"{name} must have 1 or 3 components")
+    bmn, bmx = _f3(bmin), _f3(bmax)
+    nv = (z1 - z0 + 1) * H * W
+    nc = (z1 - z0) * (H - 1) * (W - 1)
+    empty = z0 == z1 or H < 2 or W < 2
+    edge_mask = torch.empty(0 if empty else nv, dtype=torch.uint8, device=gpu)
+    vert_off = torch.empty(0 if empty else nv + 1, dtype=torch.int32, device=gpu)
+    tri_off = torch.empty(0 if empty else nc + 1, dtype=torch.int32, device=gpu)
+    totals = np.zeros(2, np.int64)
+    head = (ptr(T), ptr(Wt), D, H, W, z0, z1, float(iso), float(min_weight))
+    call("sfmhip_tsdf_surface_count", *head, ptr(edge_mask), ptr(vert_off), ptr(tri_off), totals.ctypes.data,
+         stream_ptr())
+    nvert, ntri = int(totals[0]), int(totals[1])
+    vertices = torch.empty((nvert, 3), dtype=torch.float32, device=gpu)
+    nrm = torch.empty((nvert, 3), dtype=torch.float32, device=gpu) if normals else None
+    faces = torch.empty((ntri, 3), dtype=torch.int32, device=gpu)
+    call("sfmhip_tsdf_surface_emit", *head, _host_ptr(bmn), _host_ptr(bmx), ptr(edge_mask), ptr(vert_off),
+         ptr(tri_off), ptr(vertices), ptr(nrm), ptr(faces), stream_ptr())
+    return vertices, nrm, faces

@@ -353,6 +353,85 @@ int sfmhip_tsdf_layer_stats(int D, int H, int W, const float* depth, int F, int 
                             const float* poses, const float* Kf, const float* bmin, const float* bmax,
                             float trunc, int64_t* layer_stats, void* stream);
 
+/* ---- V6: triangle mesh of the fused TSDF grid (build-defined) -------------
+ * Marching tetrahedra on the Kuhn (Freudenthal) 6-tetrahedron split of every
+ * cell: 16 cases per tetrahedron, no ambiguous case, neighbouring cells agree
+ * on shared faces, so the mesh is a consistently oriented 2-manifold.  The
+ * reference's final artefact is a .ply (sfm.py:54-77, numpy2ply.py); it has no
+ * volumetric surface.  Restated in numpy by tests/surface_ref.py.
+ *
+ * Inputs: T, Wt (D,H,W) f32 as sfmhip_tsdf_integrate leaves them (x -> W,
+ * y -> H, z -> D, align_corners; Wt == 0: never observed; T positive in free
+ * space); HOST float[3] bounds bmin / bmax; iso; min_weight (<= 0 is
+ * SFMHIP_E_ARG); a cell-layer range [z0, z1), 0 <= z0 <= z1 <= D-1.
+ *
+ * Voxels and cells: voxel (z,y,x) has linear id (z*H + y)*W + x.
+ * observed(v): Wt[v] >= min_weight and T[v] finite.  inside(v): T[v] < iso.
+ * Cell (z,y,x) exists for z in [z0,z1), y < H-1, x < W-1; its corners are the
+ * 8 voxels at offsets in {0,1}^3; it is VALID when all 8 are observed; its
+ * linear id is (z*(H-1) + y)*(W-1) + x.
+ *
+ * Edge slots: each voxel owns 7, slot k with offset (dx,dy,dz):
+ *   0 (1,0,0)  1 (0,1,0)  2 (0,0,1)  3 (1,1,0)  4 (1,0,1)  5 (0,1,1)  6 (1,1,1)
+ * (every edge of every Kuhn tetrahedron is one of these).  Edge (v,k) is ACTIVE
+ * when v+o_k is in the grid, inside(v) != inside(v+o_k), and at least one valid
+ * cell of this call's range has both endpoints among its corners (4 candidate
+ * cells for axis edges, 2 for face diagonals, 1 for the body diagonal).
+ *
+ * Vertices: one per active edge, ordered by (voxel linear id, k).  f32, no
+ * FMA, op by op: s = (iso - T[v]) / (T[v+o] - T[v]); per axis
+ * g = f32(idx) + s*f32(o), p = bmin + g*step, step = (bmax - bmin)/f32(R-1).
+ *
+ * Normals (optional): for voxel u and axis a the gradient is the central
+ * difference (T[u+e_a] - T[u-e_a]) / (2 step_a) when both neighbours are in
+ * the grid (the whole grid passed in, not the range) and observed, the
+ * one-sided difference over step_a when one is, 0 when neither.  The vertex
+ * normal is normalize((1-s) g(v) + s g(v+o)), (0,0,0) when the length is 0 or
+ * not finite; it points towards increasing T (free space).
+ *
+ * Tetrahedra: 6 per cell; tetrahedron t is the lexicographic rank of the axis
+ * permutation (a,b,c) of (x,y,z); its corners are c0 (the cell origin),
+ * c1 = c0+e_a, c2 = c1+e_b, c3 = c0+(1,1,1).
+ *
+ * Triangles: only valid cells emit.  With tetrahedron corner indices ascending:
+ *   0 or 4 corners inside: nothing;
+ *   1 inside (i; outside o1<o2<o3): (i-o1, i-o2, i-o3);
+ *   3 inside (i1<i2<i3; outside o): (i1-o, i2-o, i3-o);
+ *   2 inside (p<q; outside r<s):    (pr, ps, qs) and (pr, qs, qr);
+ * the last two vertices swapped where needed so that (v1-v0)x(v2-v0) points
+ * towards the outside corners (a function of (t, case) only: a generated 6x16
+ * bit table).  Order: cell linear id, then t, then the order above.  Face
+ * indices refer to this call's vertex array.  Zero-area triangles (T == iso at
+ * a corner) are kept.
+ *
+ * Slabs: for any partition of [0, D-1) into ranges, the concatenated per-call
+ * triangle soups vertices[faces] (and the normals at those corners) are
+ * bit-identical to the whole-grid call's; boundary vertices are duplicated
+ * between calls.  A rank needs its slab plus one neighbouring voxel layer
+ * (two for identical normals on the boundary layer).
+ *
+ * Count, then fill (like sfmhip_voxel_traversal_count / _traversal).  The work
+ * arrays are the caller's, 16-byte aligned, indexed relative to the range
+ * (NV = (z1-z0+1)*H*W voxels of layers z0..z1, NC = (z1-z0)*(H-1)*(W-1) cells):
+ *   edge_mask u8 [NV]    bit k = edge (v,k) active
+ *   vert_off i32 [NV+1]  first vertex of each voxel; [NV] = total vertices
+ *   tri_off  i32 [NC+1]  first triangle of each cell; [NC] = total triangles
+ * sfmhip_tsdf_surface_count fills them and returns HOST int64 totals[2] =
+ * (vertices, triangles); it synchronises the stream.  A total above INT32_MAX
+ * (or NV >= INT32_MAX) is SFMHIP_E_OVERFLOW: split the range.  Deterministic:
+ * plain multi-kernel scans, no atomics.
+ * sfmhip_tsdf_surface_emit (same grids, range, iso, min_weight and work
+ * arrays) writes vertices [V][3] f32, normals [V][3] f32 (nullable) and faces
+ * [F][3] i32; vertices / normals / faces may be null when their total is 0.
+ * z0 == z1, H == 1 or W == 1: no cells, totals 0, nothing is read or written. */
+int sfmhip_tsdf_surface_count(const float* T, const float* Wt, int D, int H, int W, int z0, int z1,
+                              float iso, float min_weight, uint8_t* edge_mask, int32_t* vert_off,
+                              int32_t* tri_off, int64_t* totals /* HOST [2] */, void* stream);
+int sfmhip_tsdf_surface_emit(const float* T, const float* Wt, int D, int H, int W, int z0, int z1,
+                             float iso, float min_weight, const float* bmin, const float* bmax,
+                             const uint8_t* edge_mask, const int32_t* vert_off, const int32_t* tri_off,
+                             float* vertices, float* normals /* nullable */, int32_t* faces, void* stream);
+
 /* ---- §8f row 2: geometric verification (batched over image pairs) --------
  * cv2.findEssentialMat(pts0, pts1, K, method=cv2.RANSAC, prob=0.999,
  * threshold=1) at matching.py:134 and sfm.py:108 (OpenCV five-point.cpp +
