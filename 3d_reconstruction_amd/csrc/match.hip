@@ -53,6 +53,13 @@ __device__ __forceinline__ int med3i(int a, int b, int c) {
     return r;
 }
 
+// med3 issued after `dep` is computed (an ordering-only operand: see match_kernel's value-only form)
+__device__ __forceinline__ int med3i_after(int a, int b, int c, int dep) {
+    int r;
+    asm("v_med3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c), "v"(dep));
+    return r;
+}
+
 // ---------------------------------------------------------------------------
 // Quantisation f32 -> int8 (padded rows zeroed).  4 elements per thread.
 __global__ void quantize_kernel(const float* __restrict__ in, int64_t total, int d, int m_pad,
@@ -199,6 +206,11 @@ struct CertArgs {
     int force;            // 1: no row is certified (every row takes the exact path; tests)
 };
 constexpr int kUndecidedBase = -3;   // matches0 = kUndecidedBase - D2 marks an undecided row
+// match_kernel's value-only form: 16-candidate tiles per recorded winner range (a lane sees 4
+// distances per tile, so G = 16 per range; 8 tiles = one range per 128-row block).  Measured on
+// C3, 1 / 2 / 4 / 8 tiles: 92.3 / 91.3 / 90.3 / 90.3 ms on all pairs, 1.75 / 1.73 / 1.73 / 1.80 ms
+// on the overlapping pairs (profiles/r7/match_valueonly_ab.txt)
+constexpr int kValueOnlyTiles = 4;
 // int16 graphs (m_pad <= 32767: dist.graph_dtype) carry an upper bound of sqrt(D2) instead:
 // mark = kUndecidedBase - u, u = ceil(8 sqrt(D2)) <= 32640 for d <= 256 (D2 <= 256 * 255^2),
 // so the mark stays above -32768 and the resolve's candidate radius only grows (by < 1/8).
@@ -221,12 +233,16 @@ __device__ __forceinline__ double mark_sqrt_d2(int mark) {
     else return sqrt((double)(kUndecidedBase - mark));
 }
 
-// 1 accept, 0 reject, -1 undecided
-__device__ __forceinline__ int certify(int d1, int d2, double E, double inv_s, double rn2, double rd2) {
+// 1 accept, 0 reject, -1 undecided.  Each integer distance is given as an interval
+// [lo, hi] (lo == hi in the packed-key form, hi - lo = 1 in the value-only form below): the
+// lower bounds come from lo, the upper bounds from hi.
+__device__ __forceinline__ int certify(int d1lo, int d1hi, int d2lo, int d2hi, double E, double inv_s, double rn2,
+                                       double rd2) {
     const double up = 1.0 + 0x1p-50, dn = 1.0 - 0x1p-50;
-    const double s1 = sqrt((double)d1) * inv_s, s2 = sqrt((double)d2) * inv_s;
-    const double a1 = fmax(s1 * dn - E * up, 0.0), b1 = (s1 + E) * up;
-    const double a2 = fmax(s2 * dn - E * up, 0.0), b2 = (s2 + E) * up;
+    const double s1l = sqrt((double)d1lo) * inv_s, s1h = sqrt((double)d1hi) * inv_s;
+    const double s2l = sqrt((double)d2lo) * inv_s, s2h = sqrt((double)d2hi) * inv_s;
+    const double a1 = fmax(s1l * dn - E * up, 0.0), b1 = (s1h + E) * up;
+    const double a2 = fmax(s2l * dn - E * up, 0.0), b2 = (s2h + E) * up;
     const double wl = 1.0 - 1e-12, wh = 1.0 + 1e-12;
     const double lo1 = a1 * a1 * wl, hi1 = b1 * b1 * wh, lo2 = a2 * a2 * wl, hi2 = b2 * b2 * wh;
     if (rd2 * lo1 >= rn2 * hi2) return 0;
@@ -237,7 +253,21 @@ __device__ __forceinline__ int certify(int d1, int d2, double E, double inv_s, d
 // One workgroup = one pair x (WAVES * NS * MF) query rows of image a.  Each
 // wave owns NS column tiles of MF query rows as resident B-operand fragments
 // and streams image b's 128-row blocks from the LDS ring (LDS-DMA filled).
-template <int D, int MF, int NS, int WAVES, bool CERT = false, typename OutT = int32_t>
+//
+// VG > 0 (certifying build without distance outputs, match_exact_impl): the value-only form.
+// The int8 pass is only a filter there, so the candidate's index is not carried through the
+// top-2.  With keys[j] = (-nb_j << 7) | low, h_j = keys[j] >> 8 and p_j = (keys[j] >> 7) & 1
+// give -nb_j = 2 h_j + p_j.  Each accumulator chain starts from h_j instead of 0, so
+//   acc = <b_j, a_i> + h_j =: v,   D_ij = na_i - 2 v - p_j  in  {Du - 1, Du},  Du = na_i - 2 v
+// (padded rows: dot 0, h = -2^23, below every valid v; |v| < 2^24).  The top two of the raw v
+// run over the whole candidate stream (1.25 VALU per distance, no packing, no per-block merge);
+// per VG candidate tiles a lane records whether its best rose (the range id).  The certificate
+// takes D1 in [Du1 - 1, Du1] and D2 in [Du2 - 1, Du2]: the best-v candidate w has D_w <= Du1 and
+// every other candidate D_j >= Du2 - 1, so an accept (hi(Du1) < lo(Du2 - 1), which needs
+// v1 > v2) proves w the unique winner, and equal values are never accepted.  Only accepted rows
+// need w's index: the wave recomputes <b_j, a_i> + h_j for the 4 VG candidates of the recorded
+// range and takes the one equal to v1.  Undecided rows carry Du2 >= D2 in their mark.
+template <int D, int MF, int NS, int WAVES, bool CERT = false, typename OutT = int32_t, int VG = 0>
 __global__ __launch_bounds__(64 * WAVES, 2) void match_kernel(
     const int8_t* __restrict__ desc, const int32_t* __restrict__ norms,
     const int32_t* __restrict__ keys, const int32_t* __restrict__ nk, int m_pad,
@@ -255,6 +285,8 @@ __global__ __launch_bounds__(64 * WAVES, 2) void match_kernel(
     constexpr int IB = IW * WAVES;                  // query rows per workgroup
     constexpr int JT = kJB / MF;                    // candidate tiles per block
     static_assert(NS % NG == 0 || NG % NS == 0, "output lane mapping");
+    constexpr bool VO = VG > 0;
+    static_assert(!VO || (CERT && M::NREG == 4 && NS == NG && JT % VG == 0), "value-only form: 16x16 tiles, NS == NG");
 
     __shared__ __attribute__((aligned(16))) int8_t lds[2 * TILE + 2 * kJB * 4];
 
@@ -298,6 +330,9 @@ __global__ __launch_bounds__(64 * WAVES, 2) void match_kernel(
     int g1k[NS], g1i[NS], g2k[NS], g1w[NS], g1b[NS];   // best key, its packed word and block; second key
 #pragma unroll
     for (int s = 0; s < NS; ++s) { g1k[s] = INT_MIN; g1i[s] = 0; g1w[s] = 127; g1b[s] = 0; g2k[s] = INT_MIN; }
+    int w1[NS], w2[NS], wr[NS];   // value-only form: the stream's top two values, the range where the best rose
+#pragma unroll
+    for (int s = 0; s < NS; ++s) { w1[s] = INT_MIN; w2[s] = INT_MIN; wr[s] = 0; }
 
     __syncthreads();
 
@@ -308,6 +343,49 @@ __global__ __launch_bounds__(64 * WAVES, 2) void match_kernel(
                    kbase + (cur ^ 1) * kJB, wave, lane);
         const int8_t* tl = lds + cur * TILE;
         const int32_t* kl = kbase + cur * kJB;
+        if constexpr (VO) {
+            int p1[NS];
+#pragma unroll
+            for (int jt = 0; jt < JT; ++jt) {
+                if (jt % VG == 0) {
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) p1[s] = w1[s];
+                }
+                // the lane's four candidate rows of this tile: h_j starts every chain
+                const i32x4 hv = *reinterpret_cast<const i32x4*>(kl + jt * MF + M::row(0, grp)) >> 8;
+                acc_t acc[NS];
+#pragma unroll
+                for (int s = 0; s < NS; ++s) acc[s] = hv;
+                const int r = jt * MF + lr;
+#pragma unroll
+                for (int kk = 0; kk < KK; ++kk) {
+                    const i32x4 av = *reinterpret_cast<const i32x4*>(tl + swz_off<D>(r, kk * CPK + grp));
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) acc[s] = M::run(av, bq[s][kk], acc[s]);
+                }
+                // with w1 >= w2 the top two of {w1, w2, a, b} are max3(w1, a, b) and max(w2, med3(w1, a, b)),
+                // equal values included (w1 == w2 when the maximum occurs twice): 5 VALU per 4 distances.
+                // The accumulators' first reader is plain C++ (the two max, selected as v_max3_i32): the
+                // compiler keeps the MFMA -> VALU read distance only for instructions it can see, not
+                // for inline asm, so each med3 is ordered behind that read by a dummy operand.
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    const int n1 = max(max(w1[s], acc[s][0]), acc[s][1]);
+                    const int m = med3i_after(w1[s], acc[s][0], acc[s][1], n1);
+                    const int n2 = max(max(n1, acc[s][2]), acc[s][3]);
+                    const int m2 = med3i_after(n1, acc[s][2], acc[s][3], n2);
+                    w1[s] = n2;
+                    w2[s] = max3i(w2[s], m, m2);
+                }
+                if (jt % VG == VG - 1) {
+                    const int rid = blk * (JT / VG) + jt / VG;
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) wr[s] = w1[s] > p1[s] ? rid : wr[s];
+                }
+            }
+            __syncthreads();  // drains this wave's DMA; next block visible to all waves
+            continue;
+        }
         int t1[NS], t2[NS];
 #pragma unroll
         for (int s = 0; s < NS; ++s) { t1[s] = INT_MIN; t2[s] = INT_MIN; }
@@ -365,6 +443,72 @@ __global__ __launch_bounds__(64 * WAVES, 2) void match_kernel(
         __syncthreads();  // drains this wave's DMA; next block visible to all waves
     }
 
+    if constexpr (VO) {
+        // lanes of the NG groups hold the same query row, disjoint candidate rows: a value-only
+        // merge that carries the (range, lane group) of the larger best; lane group s keeps tile s
+        int v1 = INT_MIN, v2 = INT_MIN, loc = 0;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            int a1 = w1[s], a2 = w2[s], al = wr[s] * NG + grp;
+#pragma unroll
+            for (int off = MF; off < 64; off <<= 1) {
+                const int o1 = __shfl_xor(a1, off), o2 = __shfl_xor(a2, off), ol = __shfl_xor(al, off);
+                const bool mine = a1 > o1 || (a1 == o1 && al < ol);
+                a2 = max3i(min(a1, o1), a2, o2);
+                al = mine ? al : ol;
+                a1 = max(a1, o1);
+            }
+            if (s == grp) { v1 = a1; v2 = a2; loc = al; }
+        }
+        const int i = ibase + grp * MF + lr;
+        int res = -1;
+        bool accepted = false;
+        if (i < na_rows) {   // na_rows <= m_pad
+            const int na = norms[(size_t)a * m_pad + i];
+            const int du1 = na - 2 * v1, du2 = na - 2 * v2;   // D1 in [du1 - 1, du1], D2 in [du2 - 1, du2]
+            const int v = ca.force ? -1
+                                   : certify(max(du1 - 1, 0), du1, max(du2 - 1, 0), du2,
+                                             ca.erow[(size_t)a * m_pad + i] + ca.eimg[b], ca.inv_s, (double)rn2,
+                                             (double)rd2);
+            accepted = v > 0;
+            // an accepted row keeps the mark unless exactly one candidate of its range attains v1
+            res = v == 0 ? -1 : undecided_mark<OutT>(du2);
+        }
+        // index recovery, accepted rows only, one row at a time by the whole wave: LPC lanes per
+        // candidate of the recorded range, each a D / LPC byte slice of <b_j, a_i>
+        constexpr int NC = 4 * VG;
+        constexpr int LPC = (64 / NC) < (D / 16) ? (64 / NC) : (D / 16);
+        constexpr int BPL = D / LPC;
+        const int c = min(lane / LPC, NC - 1), part = lane % LPC;
+        unsigned long long bal = __ballot(accepted);
+        while (bal) {
+            const int l = __builtin_ctzll(bal);
+            bal &= bal - 1;
+            const int ri = __shfl(i, l), rv = __shfl(v1, l), rl = __shfl(loc, l);
+            const int j0 = (rl / NG) * VG * MF + 4 * (rl % NG);   // candidate c: tile c / 4 of the range, row c % 4
+            const int j = j0 + (c >> 2) * MF + (c & 3);
+            const int8_t* pa = desc + ((size_t)a * m_pad + ri) * D + part * BPL;
+            const int8_t* pb = bdesc + (size_t)j * D + part * BPL;
+            int dot = 0;
+#pragma unroll
+            for (int w = 0; w < BPL / 16; ++w) {
+                const i32x4 x = *reinterpret_cast<const i32x4*>(pa + 16 * w);
+                const i32x4 y = *reinterpret_cast<const i32x4*>(pb + 16 * w);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) dot = __builtin_amdgcn_sdot4(x[e], y[e], dot, false);
+            }
+#pragma unroll
+            for (int off = 1; off < LPC; off <<= 1) dot += __shfl_xor(dot, off);
+            const bool hit = lane < NC * LPC && part == 0 && dot + (bkeys[j] >> 8) == rv;
+            const unsigned long long hb = __ballot(hit);
+            if (lane == l && __popcll(hb) == 1) {
+                const int hc = __builtin_ctzll(hb) / LPC;
+                res = j0 + (hc >> 2) * MF + (hc & 3);
+            }
+        }
+        if (i < m_pad) out_m[i] = (OutT)res;
+        return;
+    }
     if constexpr (D <= 128) {
 #pragma unroll
         for (int s = 0; s < NS; ++s) g1i[s] = g1b[s] * kJB + 127 - (g1w[s] & 127);
@@ -393,7 +537,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void match_kernel(
             d2 = na - g2k[s];
             if (CERT) {
                 const int v = ca.force ? -1
-                                       : certify(d1, d2, ca.erow[(size_t)a * m_pad + i] + ca.eimg[b], ca.inv_s,
+                                       : certify(d1, d1, d2, d2, ca.erow[(size_t)a * m_pad + i] + ca.eimg[b], ca.inv_s,
                                                  (double)rn2, (double)rd2);
                 res = v > 0 ? g1i[s] : (v == 0 ? -1 : undecided_mark<OutT>(d2));
             } else if (rd2 * (long long)d1 < rn2 * (long long)d2) {
@@ -1497,6 +1641,8 @@ static int match_pairs_impl(const int8_t* desc, const int32_t* norms, const int3
     SFMHIP_REQUIRE(m_pad > 0 && m_pad % kJB == 0, "sfmhip_match_pairs: m_pad must be a positive multiple of 128");
     SFMHIP_REQUIRE(ratio_num > 0 && ratio_den > 0 && ratio_num <= 65535 && ratio_den <= 65535,
                    "sfmhip_match_pairs: ratio must be a positive fraction");
+    if constexpr (sizeof(OutT) == 2)
+        SFMHIP_REQUIRE(m_pad <= 32767, "sfmhip_match_pairs_i16: m_pad must be <= 32767 for an int16 graph");
     if (P == 0) return SFMHIP_OK;
     SFMHIP_REQUIRE(desc && norms && keys && n_kpts && pairs && matches0,
                    "sfmhip_match_pairs: null pointer");
@@ -1508,8 +1654,6 @@ static int match_pairs_impl(const int8_t* desc, const int32_t* norms, const int3
     const int nwg = (int)nwg64;
     const long long rn2 = (long long)ratio_num * ratio_num, rd2 = (long long)ratio_den * ratio_den;
     hipStream_t s = as_stream(stream);
-    if constexpr (sizeof(OutT) == 2)
-        SFMHIP_REQUIRE(m_pad <= 32767, "sfmhip_match_pairs_i16: m_pad must be <= 32767 for an int16 graph");
 #define SFMHIP_LAUNCH_MATCH(DD, MF, NS, WW)                                                              \
     hipLaunchKernelGGL((match_kernel<DD, MF, NS, WW, false, OutT>), dim3(nwg), dim3(64 * WW), 0, s, desc, norms, keys, \
                        n_kpts, m_pad, pairs, n_iblk, nwg, rn2, rd2, matches0, dist1, dist2, CertArgs{})
@@ -1699,9 +1843,16 @@ static int match_exact_impl(const int8_t* desc, const int32_t* norms, const int3
         return check_launch("memset");
     }
     const int rxgrid = n_cu * 2;   // a multiple of 8: every XCD gets the same number of blocks
+    // no distance outputs (the int16 graph; dist.match_all_pairs_sharded): the value-only form
+    const bool value_only = !dist1 && !dist2;
 #define SFMHIP_LAUNCH_EXACT(DD)                                                                                  \
-    hipLaunchKernelGGL((match_kernel<DD, 16, 4, 4, true, OutT>), dim3(nwg), dim3(256), 0, s, desc, norms, keys, n_kpts, \
-                       m_pad, pairs, n_iblk, nwg, rn2, rd2, matches0, dist1, dist2, ca);                         \
+    if (value_only) {                                                                                             \
+        hipLaunchKernelGGL((match_kernel<DD, 16, 4, 4, true, OutT, kValueOnlyTiles>), dim3(nwg), dim3(256), 0, s, desc, \
+                           norms, keys, n_kpts, m_pad, pairs, n_iblk, nwg, rn2, rd2, matches0, dist1, dist2, ca);  \
+    } else {                                                                                                      \
+        hipLaunchKernelGGL((match_kernel<DD, 16, 4, 4, true, OutT>), dim3(nwg), dim3(256), 0, s, desc, norms, keys, \
+                           n_kpts, m_pad, pairs, n_iblk, nwg, rn2, rd2, matches0, dist1, dist2, ca);              \
+    }                                                                                                             \
     if (int rc = check_launch("match_kernel<cert>")) {                                                          \
         scratch_free(rbuf, s);                                                                                    \
         return rc;                                                                                                \
