@@ -53,13 +53,6 @@ __device__ __forceinline__ int med3i(int a, int b, int c) {
     return r;
 }
 
-// med3 issued after `dep` is computed (an ordering-only operand: see match_kernel's value-only form)
-__device__ __forceinline__ int med3i_after(int a, int b, int c, int dep) {
-    int r;
-    asm("v_med3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c), "v"(dep));
-    return r;
-}
-
 // ---------------------------------------------------------------------------
 // Quantisation f32 -> int8 (padded rows zeroed).  4 elements per thread.
 __global__ void quantize_kernel(const float* __restrict__ in, int64_t total, int d, int m_pad,
@@ -117,6 +110,12 @@ __global__ void prepare_kernel(const int8_t* __restrict__ desc, int n_rows, int 
     norms[row] = s;
     const int low = 127 - (r & (kJB - 1));
     keys[row] = (r < nk[img]) ? (-s * 128 + low) : (INT_MIN + low);
+}
+
+// h = keys >> 8 (match_kernel's value-only form), one call's scratch.
+__global__ void key_values_kernel(const int32_t* __restrict__ keys, int64_t n, int32_t* __restrict__ h) {
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x)
+        h[e] = keys[e] >> 8;
 }
 
 // ---------------------------------------------------------------------------
@@ -207,9 +206,10 @@ struct CertArgs {
 };
 constexpr int kUndecidedBase = -3;   // matches0 = kUndecidedBase - D2 marks an undecided row
 // match_kernel's value-only form: 16-candidate tiles per recorded winner range (a lane sees 4
-// distances per tile, so G = 16 per range; 8 tiles = one range per 128-row block).  Measured on
-// C3, 1 / 2 / 4 / 8 tiles: 92.3 / 91.3 / 90.3 / 90.3 ms on all pairs, 1.75 / 1.73 / 1.73 / 1.80 ms
-// on the overlapping pairs (profiles/r7/match_valueonly_ab.txt)
+// distances per tile, so G = 16 per range; 8 tiles = one range per 128-row block).  The loop takes
+// one maximum per range and the post-loop rescan covers one range's G candidates per surviving
+// row.  Measured on C3, 4 / 8 tiles: 81.7 / 82.7 ms on all pairs, 1.63 / 1.75 ms on the overlapping
+// pairs (profiles/r8/match_rangemax_ab.txt)
 constexpr int kValueOnlyTiles = 4;
 // int16 graphs (m_pad <= 32767: dist.graph_dtype) carry an upper bound of sqrt(D2) instead:
 // mark = kUndecidedBase - u, u = ceil(8 sqrt(D2)) <= 32640 for d <= 256 (D2 <= 256 * 255^2),
@@ -257,16 +257,30 @@ __device__ __forceinline__ int certify(int d1lo, int d1hi, int d2lo, int d2hi, d
 // VG > 0 (certifying build without distance outputs, match_exact_impl): the value-only form.
 // The int8 pass is only a filter there, so the candidate's index is not carried through the
 // top-2.  With keys[j] = (-nb_j << 7) | low, h_j = keys[j] >> 8 and p_j = (keys[j] >> 7) & 1
-// give -nb_j = 2 h_j + p_j.  Each accumulator chain starts from h_j instead of 0, so
+// give -nb_j = 2 h_j + p_j (match_exact_impl passes the array h, key_values_kernel, as `keys`:
+// the form uses the keys in no other way).  Each accumulator chain starts from h_j instead of 0, so
 //   acc = <b_j, a_i> + h_j =: v,   D_ij = na_i - 2 v - p_j  in  {Du - 1, Du},  Du = na_i - 2 v
-// (padded rows: dot 0, h = -2^23, below every valid v; |v| < 2^24).  The top two of the raw v
-// run over the whole candidate stream (1.25 VALU per distance, no packing, no per-block merge);
-// per VG candidate tiles a lane records whether its best rose (the range id).  The certificate
-// takes D1 in [Du1 - 1, Du1] and D2 in [Du2 - 1, Du2]: the best-v candidate w has D_w <= Du1 and
-// every other candidate D_j >= Du2 - 1, so an accept (hi(Du1) < lo(Du2 - 1), which needs
-// v1 > v2) proves w the unique winner, and equal values are never accepted.  Only accepted rows
-// need w's index: the wave recomputes <b_j, a_i> + h_j for the 4 VG candidates of the recorded
-// range and takes the one equal to v1.  Undecided rows carry Du2 >= D2 in their mark.
+// (padded rows: dot 0, h = -2^23, below every valid v; |v| < 2^24).  The certificate takes D1 in
+// [Du1 - 1, Du1] and D2 in [Du2 - 1, Du2], v1 >= v2 the two largest values of the row (as a
+// multiset): the best-v candidate w has D_w <= Du1 and every other candidate D_j >= Du2 - 1, so
+// an accept (hi(Du1) < lo(Du2 - 1), which needs v1 > v2) proves w the unique winner, and equal
+// values are never accepted.  Undecided rows carry Du2 >= D2 in their mark.
+//
+// The loop keeps no per-distance top two.  A group is a lane's 4 VG values of one range (4 rows
+// x VG candidate tiles); the loop takes each group's maximum (0.5 VALU per distance), and per
+// range the top two w1 >= w2 of the maxima and the range where w1 rose (strictly: the earliest
+// on ties).  After the lane-group merge v1 = the largest group maximum is the row's exact best,
+// `loc` one group that attains it, and v2' = the second of the maxima (as a multiset) = the
+// largest value outside `loc`.  A value is missing from the maxima only if its group holds a
+// larger or equal one, so the row's true second is v2 = max(v2', x), x the second largest value
+// of the group `loc` itself (x = v1 when v1 occurs twice there; when v1 is the maximum of two
+// groups, v2' = v1 already).  v2' <= v2 gives Du2ub = na - 2 v2' >= Du2: a reject on
+// (Du1, Du2ub) is final (the reject test reads lo(D1) and hi(D2) only, and hi() grows with its
+// argument, so the exact Du2 rejects too).  For the rows that survive (< 1 % on C3) the wave
+// recomputes u_c = <b_j, a_i> + h_j for the 4 VG candidates of `loc`: exactly one u_c == v1
+// gives the winner's index and x = the largest other u_c, two or more give x = v1.  The row is
+// then certified on the exact (Du1, Du2), the pair a per-distance top two gives, so the graph
+// and the marks do not depend on the grouping.
 template <int D, int MF, int NS, int WAVES, bool CERT = false, typename OutT = int32_t, int VG = 0>
 __global__ __launch_bounds__(64 * WAVES, 2) void match_kernel(
     const int8_t* __restrict__ desc, const int32_t* __restrict__ norms,
@@ -330,7 +344,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void match_kernel(
     int g1k[NS], g1i[NS], g2k[NS], g1w[NS], g1b[NS];   // best key, its packed word and block; second key
 #pragma unroll
     for (int s = 0; s < NS; ++s) { g1k[s] = INT_MIN; g1i[s] = 0; g1w[s] = 127; g1b[s] = 0; g2k[s] = INT_MIN; }
-    int w1[NS], w2[NS], wr[NS];   // value-only form: the stream's top two values, the range where the best rose
+    int w1[NS], w2[NS], wr[NS];   // value-only form: the top two of the group maxima, the range where the best rose
 #pragma unroll
     for (int s = 0; s < NS; ++s) { w1[s] = INT_MIN; w2[s] = INT_MIN; wr[s] = 0; }
 
@@ -344,15 +358,15 @@ __global__ __launch_bounds__(64 * WAVES, 2) void match_kernel(
         const int8_t* tl = lds + cur * TILE;
         const int32_t* kl = kbase + cur * kJB;
         if constexpr (VO) {
-            int p1[NS];
+            int rm[NS];   // the running maximum of the lane's 4 VG values of this range
 #pragma unroll
             for (int jt = 0; jt < JT; ++jt) {
                 if (jt % VG == 0) {
 #pragma unroll
-                    for (int s = 0; s < NS; ++s) p1[s] = w1[s];
+                    for (int s = 0; s < NS; ++s) rm[s] = INT_MIN;
                 }
                 // the lane's four candidate rows of this tile: h_j starts every chain
-                const i32x4 hv = *reinterpret_cast<const i32x4*>(kl + jt * MF + M::row(0, grp)) >> 8;
+                const i32x4 hv = *reinterpret_cast<const i32x4*>(kl + jt * MF + M::row(0, grp));
                 acc_t acc[NS];
 #pragma unroll
                 for (int s = 0; s < NS; ++s) acc[s] = hv;
@@ -363,24 +377,25 @@ __global__ __launch_bounds__(64 * WAVES, 2) void match_kernel(
 #pragma unroll
                     for (int s = 0; s < NS; ++s) acc[s] = M::run(av, bq[s][kk], acc[s]);
                 }
-                // with w1 >= w2 the top two of {w1, w2, a, b} are max3(w1, a, b) and max(w2, med3(w1, a, b)),
-                // equal values included (w1 == w2 when the maximum occurs twice): 5 VALU per 4 distances.
-                // The accumulators' first reader is plain C++ (the two max, selected as v_max3_i32): the
-                // compiler keeps the MFMA -> VALU read distance only for instructions it can see, not
-                // for inline asm, so each med3 is ordered behind that read by a dummy operand.
+                // 2 VALU per 4 distances.  The accumulators are read by plain C++ only (the two max,
+                // selected as v_max3_i32): the compiler keeps the MFMA -> VALU read distance only for
+                // instructions it can see, not for inline asm (reading the accumulators straight into
+                // an asm returned stale values on the device).
 #pragma unroll
                 for (int s = 0; s < NS; ++s) {
-                    const int n1 = max(max(w1[s], acc[s][0]), acc[s][1]);
-                    const int m = med3i_after(w1[s], acc[s][0], acc[s][1], n1);
-                    const int n2 = max(max(n1, acc[s][2]), acc[s][3]);
-                    const int m2 = med3i_after(n1, acc[s][2], acc[s][3], n2);
-                    w1[s] = n2;
-                    w2[s] = max3i(w2[s], m, m2);
+                    rm[s] = max(max(rm[s], acc[s][0]), acc[s][1]);
+                    rm[s] = max(max(rm[s], acc[s][2]), acc[s][3]);
                 }
+                // per range: with w1 >= w2 the second of {w1, w2, r} is med3(w1, w2, r), equal values
+                // included; the best's range moves only on a strict rise (the earliest range on ties)
                 if (jt % VG == VG - 1) {
                     const int rid = blk * (JT / VG) + jt / VG;
 #pragma unroll
-                    for (int s = 0; s < NS; ++s) wr[s] = w1[s] > p1[s] ? rid : wr[s];
+                    for (int s = 0; s < NS; ++s) {
+                        wr[s] = rm[s] > w1[s] ? rid : wr[s];
+                        w2[s] = med3i(w1[s], w2[s], rm[s]);
+                        w1[s] = max(w1[s], rm[s]);
+                    }
                 }
             }
             __syncthreads();  // drains this wave's DMA; next block visible to all waves
@@ -460,27 +475,35 @@ __global__ __launch_bounds__(64 * WAVES, 2) void match_kernel(
             }
             if (s == grp) { v1 = a1; v2 = a2; loc = al; }
         }
+        // v1 is the exact best; v2 (the second of the group maxima) is the largest value outside
+        // the group `loc`, a lower bound of the true second
         const int i = ibase + grp * MF + lr;
-        int res = -1;
-        bool accepted = false;
+        int res = -1, na = 0, du1 = 0, hidx = -1;
+        double E = 0.0;
+        bool survivor = false;
         if (i < na_rows) {   // na_rows <= m_pad
-            const int na = norms[(size_t)a * m_pad + i];
-            const int du1 = na - 2 * v1, du2 = na - 2 * v2;   // D1 in [du1 - 1, du1], D2 in [du2 - 1, du2]
-            const int v = ca.force ? -1
-                                   : certify(max(du1 - 1, 0), du1, max(du2 - 1, 0), du2,
-                                             ca.erow[(size_t)a * m_pad + i] + ca.eimg[b], ca.inv_s, (double)rn2,
-                                             (double)rd2);
-            accepted = v > 0;
-            // an accepted row keeps the mark unless exactly one candidate of its range attains v1
-            res = v == 0 ? -1 : undecided_mark<OutT>(du2);
+            na = norms[(size_t)a * m_pad + i];
+            du1 = na - 2 * v1;                  // D1 in [du1 - 1, du1]
+            const int du2ub = na - 2 * v2;      // D2 in [du1 - 1, du2ub]
+            E = ca.erow[(size_t)a * m_pad + i] + ca.eimg[b];
+            // pre-test: a reject reads lo(D1) and hi(D2) only, and hi() of an upper bound of D2 is
+            // valid, so 0 is final; everything else goes on.  A forced row is marked from du2ub, or
+            // from the largest int8 distance where v2 is a padded row's value (all valid candidates
+            // in one group: the int16 mark holds sqrt(D2) only up to D 255^2)
+            if (ca.force)
+                res = undecided_mark<OutT>(min(du2ub, D * 255 * 255));
+            else
+                survivor = certify(max(du1 - 1, 0), du1, max(du1 - 1, 0), du2ub, E, ca.inv_s, (double)rn2,
+                                   (double)rd2) != 0;
         }
-        // index recovery, accepted rows only, one row at a time by the whole wave: LPC lanes per
-        // candidate of the recorded range, each a D / LPC byte slice of <b_j, a_i>
+        // the hidden second and the winner's index, surviving rows only, one row at a time by the
+        // whole wave: LPC lanes per candidate of the recorded group, each a D / LPC byte slice of
+        // <b_j, a_i>
         constexpr int NC = 4 * VG;
         constexpr int LPC = (64 / NC) < (D / 16) ? (64 / NC) : (D / 16);
         constexpr int BPL = D / LPC;
         const int c = min(lane / LPC, NC - 1), part = lane % LPC;
-        unsigned long long bal = __ballot(accepted);
+        unsigned long long bal = __ballot(survivor);
         while (bal) {
             const int l = __builtin_ctzll(bal);
             bal &= bal - 1;
@@ -499,12 +522,28 @@ __global__ __launch_bounds__(64 * WAVES, 2) void match_kernel(
             }
 #pragma unroll
             for (int off = 1; off < LPC; off <<= 1) dot += __shfl_xor(dot, off);
-            const bool hit = lane < NC * LPC && part == 0 && dot + (bkeys[j] >> 8) == rv;
-            const unsigned long long hb = __ballot(hit);
-            if (lane == l && __popcll(hb) == 1) {
-                const int hc = __builtin_ctzll(hb) / LPC;
-                res = j0 + (hc >> 2) * MF + (hc & 3);
+            const int u = dot + bkeys[j];   // every lane of candidate c holds u_c
+            const bool hit = lane < NC * LPC && part == 0 && u == rv;
+            const unsigned long long hb = __ballot(hit);   // >= 1 candidate: the group's maximum is v1
+            // the largest value of the group's other candidates: v1 again when it occurs twice
+            int x = u == rv ? INT_MIN : u;
+#pragma unroll
+            for (int off = LPC; off < 64; off <<= 1) x = max(x, __shfl_xor(x, off));
+            if (lane == l) {
+                const bool one = __popcll(hb) == 1;
+                v2 = max(v2, one ? x : rv);
+                if (one) {
+                    const int hc = __builtin_ctzll(hb) / LPC;
+                    hidx = j0 + (hc >> 2) * MF + (hc & 3);
+                }
             }
+        }
+        // the final decision on the exact second, as the per-distance top two gave it
+        if (survivor) {
+            const int du2 = na - 2 * v2;   // D2 in [du2 - 1, du2]
+            const int v = certify(max(du1 - 1, 0), du1, max(du2 - 1, 0), du2, E, ca.inv_s, (double)rn2, (double)rd2);
+            // an accepted row has v1 > v2, so exactly one candidate of its group attains v1
+            res = v == 0 ? -1 : (v > 0 && hidx >= 0) ? hidx : undecided_mark<OutT>(du2);
         }
         if (i < m_pad) out_m[i] = (OutT)res;
         return;
@@ -1823,7 +1862,11 @@ static int match_exact_impl(const int8_t* desc, const int32_t* norms, const int3
     const size_t rcnt_bytes = ((size_t)n_img + 1) * sizeof(unsigned);
     const size_t roff_bytes = (3 * (size_t)n_img + 33) * sizeof(unsigned);   // off, okey (+1), oimg, xr, ir
     const size_t ritem_bytes = 3 * (size_t)n_img * (kResolveBucket / kResolveRows + 1) * sizeof(int);
-    if (scratch_alloc(&rbuf, 2 * rlist_bytes + rcnt_bytes + roff_bytes + ritem_bytes, s) != hipSuccess) {
+    // no distance outputs (the int16 graph; dist.match_all_pairs_sharded): the value-only form
+    const bool value_only = !dist1 && !dist2;
+    const size_t rbytes = 2 * rlist_bytes + rcnt_bytes + roff_bytes + ritem_bytes;   // a multiple of 4
+    const size_t hn = value_only ? (size_t)n_img * m_pad : 0;   // the value-only form's h = keys >> 8, behind the rest
+    if (scratch_alloc(&rbuf, rbytes + hn * sizeof(int32_t), s) != hipSuccess) {
         (void)hipGetLastError();
         set_error("sfmhip_match_pairs_exact: scratch allocation failed");
         return SFMHIP_E_HIP;
@@ -1843,8 +1886,12 @@ static int match_exact_impl(const int8_t* desc, const int32_t* norms, const int3
         return check_launch("memset");
     }
     const int rxgrid = n_cu * 2;   // a multiple of 8: every XCD gets the same number of blocks
-    // no distance outputs (the int16 graph; dist.match_all_pairs_sharded): the value-only form
-    const bool value_only = !dist1 && !dist2;
+    if (hn) {
+        int32_t* h = reinterpret_cast<int32_t*>(static_cast<char*>(rbuf) + rbytes);
+        hipLaunchKernelGGL(key_values_kernel, dim3(std::min(ceil_div((int64_t)hn, 256), 4096)), dim3(256), 0, s, keys,
+                           (int64_t)hn, h);
+        keys = h;
+    }
 #define SFMHIP_LAUNCH_EXACT(DD)                                                                                  \
     if (value_only) {                                                                                             \
         hipLaunchKernelGGL((match_kernel<DD, 16, 4, 4, true, OutT, kValueOnlyTiles>), dim3(nwg), dim3(256), 0, s, desc, \
