@@ -371,6 +371,60 @@ __global__ __launch_bounds__(256) void surf_vertex_kernel(const float* __restric
     }
 }
 
+// V7 vertex colours: the fused colour of voxel v, sum / n per channel (u32 -> f32 RN, IEEE
+// division); false when the voxel never took a sample
+__device__ __forceinline__ bool voxel_colour(const uint4* __restrict__ C, size_t v, float* col) {
+    const uint4 r = C[v];
+    if (r.w == 0u) return false;
+    const float n = (float)r.w;
+    col[0] = (float)r.x / n;
+    col[1] = (float)r.y / n;
+    col[2] = (float)r.z / n;
+    return true;
+}
+
+// One thread per voxel, like surf_vertex_kernel: for each active edge the same s, the two
+// endpoints' colours interpolated (the coloured one where only one is), 4 bytes per vertex.
+__global__ __launch_bounds__(256) void surf_colour_kernel(const float* __restrict__ T, const uint4* __restrict__ C,
+                                                          int D, int H, int W, int z0, int64_t nv, float iso,
+                                                          const uint8_t* __restrict__ mask,
+                                                          const int32_t* __restrict__ voff,
+                                                          uchar4* __restrict__ rgba) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nv) return;
+    const unsigned m = mask[i] & 0x7fu;
+    if (!m) return;
+    const int x = (int)(i % W), y = (int)((i / W) % H), z = z0 + (int)(i / ((int64_t)W * H));
+    const size_t c = ((size_t)z * H + y) * W + x;
+    const float t0 = T[c];
+    float ca[3] = {0.f, 0.f, 0.f};
+    const bool ha = voxel_colour(C, c, ca);
+    size_t o = (size_t)voff[i];
+    constexpr int code[7] = {1, 2, 4, 3, 5, 6, 7};
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+        if (!((m >> k) & 1u)) continue;
+        // an active edge's far endpoint is in the grid (V6); a mask that says otherwise is not followed
+        if (x + (code[k] & 1) >= W || y + ((code[k] >> 1) & 1) >= H || z + (code[k] >> 2) >= D) {
+            ++o;
+            continue;
+        }
+        const size_t c1 = ((size_t)(z + (code[k] >> 2)) * H + y + ((code[k] >> 1) & 1)) * W + x + (code[k] & 1);
+        const float t1 = T[c1];
+        const float s = (iso - t0) / (t1 - t0);
+        float cb[3] = {0.f, 0.f, 0.f};
+        const bool hb = voxel_colour(C, c1, cb);
+        unsigned char out[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float mm = ha && hb ? ca[a] + s * (cb[a] - ca[a]) : ha ? ca[a] : hb ? cb[a] : 0.f;
+            out[a] = (unsigned char)__builtin_rintf(fminf(255.f, fmaxf(0.f, mm)));
+        }
+        rgba[o] = make_uchar4(out[0], out[1], out[2], ha || hb ? 255 : 0);
+        ++o;
+    }
+}
+
 struct CellCtx {
     const uint8_t* mask;
     const int32_t* voff;
@@ -571,4 +625,22 @@ extern "C" int sfmhip_tsdf_surface_emit(const float* T, const float* Wt, int D, 
     hipLaunchKernelGGL(surf_face_kernel, dim3(ceil_div(R.nt, 256)), dim3(256), 0, st, T, H, W, z0, R.nt, iso,
                        edge_mask, vert_off, tri_off, faces);
     return check_launch("surf_face_kernel");
+}
+
+extern "C" int sfmhip_tsdf_surface_colours(const float* T, const float* Wt, const uint32_t* C, int D, int H, int W,
+                                           int z0, int z1, float iso, float min_weight, const uint8_t* edge_mask,
+                                           const int32_t* vert_off, uint8_t* rgba, void* stream) {
+    const char* fn = "sfmhip_tsdf_surface_colours";
+    Range R;
+    const int rc0 = check_args(fn, D, H, W, z0, z1, min_weight, R);
+    if (rc0 != SFMHIP_OK) return rc0;
+    if (R.empty) return SFMHIP_OK;
+    SFMHIP_REQUIRE(T && Wt && C && edge_mask && vert_off, "%s: null pointer", fn);
+    SFMHIP_REQUIRE(aligned16(C) && (reinterpret_cast<uintptr_t>(rgba) & 3u) == 0,
+                   "%s: C must be 16-byte and rgba 4-byte aligned", fn);
+    // rgba (caller-sized from the vertex total) may be null only when that total is 0
+    hipLaunchKernelGGL(surf_colour_kernel, dim3(ceil_div(R.nv, 256)), dim3(256), 0, as_stream(stream), T,
+                       reinterpret_cast<const uint4*>(C), D, H, W, z0, R.nv, iso, edge_mask, vert_off,
+                       reinterpret_cast<uchar4*>(rgba));
+    return check_launch("surf_colour_kernel");
 }

@@ -28,6 +28,8 @@
 //   tsdf_order_kernel     longest-first workgroup order per XCD class
 //   tsdf_fuse_kernel      one wave per 8x2x8 sub-tile: integer (S, n) in registers over
 //                         the step's frames, then the voxels finished in place
+//   tsdf_colour_kernel    (colour mode, V7: sfmhip_tsdf_integrate_colour) in its place: the same
+//                         evaluation of the projected frames, {sum r, sum g, sum b, n} per voxel
 // All fp32/fp64 with -ffp-contract=off so the op order matches the oracle.
 #include "common.h"
 #include <climits>
@@ -947,6 +949,17 @@ __device__ __forceinline__ void sub_voxel(int64_t sub, int ntx, int nty, int z0,
     y = by * kTsdfTY + 2 * q;
 }
 
+// World coordinates of the lane's two voxels (x, y, z) and (x, y + 1, z): align_corners.
+__device__ __forceinline__ void voxel_world(const GridBox& B, int D, int H, int W, int x, int y, int z, float& vx,
+                                            f2& vy, float& vz) {
+    const float sx = (B.mx[0] - B.mn[0]) / (float)(W - 1);
+    const float sy = (B.mx[1] - B.mn[1]) / (float)(H - 1);
+    const float sz = (B.mx[2] - B.mn[2]) / (float)(D - 1);
+    vx = B.mn[0] + (float)x * sx;
+    vy = f2{B.mn[1] + (float)y * sy, B.mn[1] + (float)(y + 1) * sy};
+    vz = B.mn[2] + (float)z * sz;
+}
+
 // The step's finish of one voxel: n updates with fixed-point sum S.
 __device__ __forceinline__ void tsdf_finish_voxel(float& t, float& w, int S, int n) {
     const double num = (double)t * (double)w + (double)S * 0x1p-21;
@@ -970,9 +983,15 @@ struct FrameCtx {
 // load drops without a cache access): projections -> block-table loads -> block
 // tests and depth loads -> tsdf.  The second voxel of a lane reads the table only
 // when its block differs from the first voxel's.
-template <bool VT, int NF>
+// COL (V7 colour fusion) replaces the last stage: a voxel takes the frame's colour iff V5
+// updates it with tsdf < 1 (f32 compare; a voxel the block test proved free space has tsdf = 1
+// exactly).  Only those band voxels gather the colour dword, at the depth gather's own offset
+// in the pixel-aligned [Hd][Wd][4] u8 frame; acc += {r, g, b, 1} modulo 2^32, q / g unused.
+template <bool VT, int NF, bool COL = false>
 __device__ __forceinline__ void frames_eval(const FrameCtx& c, const int* f, float vx, f2 vy, float vz, bool two,
-                                            int* q0, int* q1, bool* g0, bool* g1) {
+                                            int* q0, int* q1, bool* g0, bool* g1,
+                                            const unsigned* __restrict__ colour = nullptr, unsigned* acc0 = nullptr,
+                                            unsigned* acc1 = nullptr) {
     f2 Zc[NF];
     int iu0[NF], iv0[NF], iu1[NF], iv1[NF];
     bool ok0[NF], ok1[NF];
@@ -1044,6 +1063,36 @@ __device__ __forceinline__ void frames_eval(const FrameCtx& c, const int* f, flo
                      __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
                          rs, (int)(need1[k] ? __umul24(iv1[k], c.Wd4) + ((unsigned)iu1[k] << 2) : oob), 0, 0))};
     }
+    if constexpr (COL) {
+        bool b0[NF], b1[NF];
+        unsigned p0[NF], p1[NF];
+#pragma unroll
+        for (int k = 0; k < NF; ++k) {
+            const f2 sdf = dep[k] - Zc[k];
+            const f2 sc = sdf * f2s(c.inv_trunc);
+            b0[k] = need0[k] & (dep[k].x > 0.f) & !(sdf.x < -c.trunc) & (fminf(1.0f, sc.x) < 1.0f);
+            b1[k] = need1[k] & (dep[k].y > 0.f) & !(sdf.y < -c.trunc) & (fminf(1.0f, sc.y) < 1.0f);
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+                (void*)(colour + (size_t)f[k] * c.frame), (short)0, c.nbytes, 0x00020000);
+            p0[k] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(
+                rs, (int)(b0[k] ? __umul24(iv0[k], c.Wd4) + ((unsigned)iu0[k] << 2) : oob), 0, 0);
+            p1[k] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(
+                rs, (int)(b1[k] ? __umul24(iv1[k], c.Wd4) + ((unsigned)iu1[k] << 2) : oob), 0, 0);
+        }
+#pragma unroll
+        for (int k = 0; k < NF; ++k) {
+            const unsigned a = b0[k] ? p0[k] : 0u, b = b1[k] ? p1[k] : 0u;
+            acc0[0] += a & 255u;
+            acc0[1] += (a >> 8) & 255u;
+            acc0[2] += (a >> 16) & 255u;
+            acc0[3] += b0[k] ? 1u : 0u;
+            acc1[0] += b & 255u;
+            acc1[1] += (b >> 8) & 255u;
+            acc1[2] += (b >> 16) & 255u;
+            acc1[3] += b1[k] ? 1u : 0u;
+        }
+        return;
+    }
 #pragma unroll
     for (int k = 0; k < NF; ++k) {
         const f2 sdf = dep[k] - Zc[k];
@@ -1097,12 +1146,9 @@ __global__ __launch_bounds__(256) void tsdf_fuse_kernel(float* __restrict__ T, f
     if (y >= H) return;                      // wave-uniform (a ragged last tile row)
     const bool in0 = x < W && z < z1;
     const bool two = in0 && y + 1 < H;
-    const float sx = (B.mx[0] - B.mn[0]) / (float)(W - 1);
-    const float sy = (B.mx[1] - B.mn[1]) / (float)(H - 1);
-    const float sz = (B.mx[2] - B.mn[2]) / (float)(D - 1);
-    const float vx = B.mn[0] + (float)x * sx;
-    const f2 vy = {B.mn[1] + (float)y * sy, B.mn[1] + (float)(y + 1) * sy};
-    const float vz = B.mn[2] + (float)z * sz;
+    float vx, vz;
+    f2 vy;
+    voxel_world(B, D, H, W, x, y, z, vx, vy, vz);
     int S0 = 0, S1 = 0, n0 = 0, n1 = 0;
     int kfree = 0;                           // free-space frames
     int pend[NFS], np = 0;                   // projected frames waiting for a full stage
@@ -1157,6 +1203,71 @@ __global__ __launch_bounds__(256) void tsdf_fuse_kernel(float* __restrict__ T, f
     }
 }
 
+// V7 colour fusion: the fusion's work decomposition and mask walk (one wave per 8 x 2 x 8
+// sub-tile, two y-adjacent voxels per lane), evaluating only the projected frames: a culled
+// pair updates nothing and a free-space pair has tsdf = 1 everywhere, so neither can colour
+// a voxel, and a sub-tile without a projected frame returns before touching C.  Integer sums
+// {r, g, b, n} modulo 2^32 in registers, then one 16-byte read-modify-write of C per voxel
+// that took a sample: any order, slab split or batching of the frames gives the same bits.
+template <bool VT, int NFS = 2>
+__global__ __launch_bounds__(256) void tsdf_colour_kernel(uint4* __restrict__ C, const unsigned* __restrict__ colour,
+                                                          int D, int H, int W, int z0, int z1, FrameCtx c, GridBox B,
+                                                          int F, SlotMap SM, const unsigned* __restrict__ cull,
+                                                          const unsigned* __restrict__ freem, int nw,
+                                                          const unsigned* __restrict__ order) {
+    const int l = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    int tx, ty, tz;
+    if (!tsdf_slot_tile(order ? (int)order[blockIdx.x] : (int)blockIdx.x, SM, tx, ty, tz)) return;
+    const int64_t sub = (((int64_t)tz * SM.nty + ty) * SM.ntx + tx) * kCullSub + wave;
+    const size_t slot = (size_t)sub * nw;
+    {   // no projected frame for this wave: C is not even read
+        unsigned any = 0u;
+        for (int w = 0; w < nw; ++w) {
+            const int w0 = w << 5;
+            any |= ~cull[slot + w] & ~freem[slot + w] & (F - w0 >= 32 ? ~0u : ((1u << (F - w0)) - 1u));
+        }
+        if (__builtin_amdgcn_readfirstlane((int)any) == 0) return;
+    }
+    int x, y, z;
+    sub_voxel(sub, SM.ntx, SM.nty, z0, l, x, y, z);
+    if (y >= H) return;                      // wave-uniform (a ragged last tile row)
+    const bool in0 = x < W && z < z1;
+    const bool two = in0 && y + 1 < H;
+    float vx, vz;
+    f2 vy;
+    voxel_world(B, D, H, W, x, y, z, vx, vy, vz);
+    unsigned a0[4] = {0u, 0u, 0u, 0u}, a1[4] = {0u, 0u, 0u, 0u};
+    int pend[NFS], np = 0;                   // projected frames waiting for a full stage
+    for (int w = 0; w < nw; ++w) {
+        const int w0 = w << 5;
+        const unsigned live = F - w0 >= 32 ? ~0u : ((1u << (F - w0)) - 1u);
+        const unsigned todo = (unsigned)__builtin_amdgcn_readfirstlane((int)(live & ~cull[slot + w]));
+        unsigned proj = todo & ~(unsigned)__builtin_amdgcn_readfirstlane((int)freem[slot + w]);
+        while (proj) {
+            pend[np++] = w0 + __builtin_ctz(proj);
+            proj &= proj - 1u;
+            if (np < NFS) continue;
+            frames_eval<VT, NFS, true>(c, pend, vx, vy, vz, two, nullptr, nullptr, nullptr, nullptr, colour, a0, a1);
+            np = 0;
+        }
+    }
+    for (int k = 0; k < np; ++k)   // the last stage's remainder, one frame at a time
+        frames_eval<VT, 1, true>(c, pend + k, vx, vy, vz, two, nullptr, nullptr, nullptr, nullptr, colour, a0, a1);
+    if (!in0) return;
+    const size_t idx = ((size_t)z * H + y) * W + x;
+    if (a0[3] > 0u) {
+        uint4 r = C[idx];
+        r.x += a0[0]; r.y += a0[1]; r.z += a0[2]; r.w += a0[3];
+        C[idx] = r;
+    }
+    if (two && a1[3] > 0u) {
+        uint4 r = C[idx + W];
+        r.x += a1[0]; r.y += a1[1]; r.z += a1[2]; r.w += a1[3];
+        C[idx + W] = r;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // Host.  Knob (read once, sfmhip_knobs_reload re-reads it: lib.hip):
 //   SFMHIP_TSDF_LATENCY  -1 auto (default), 0 whole-grid mode, 1 latency mode
@@ -1170,13 +1281,17 @@ __global__ __launch_bounds__(256) void tsdf_fuse_kernel(float* __restrict__ T, f
 // whole image ([F][nbv][nbu] float2, sfmhip_tsdf_block_table); the block pass is skipped.
 static int tsdf_run(float* T, float* Wt, int D, int H, int W, int z0, int z1, const float* depth, int F, int Hd,
                     int Wd, const float* poses, const float* Kf, const float* bmin, const float* bmax, float trunc,
-                    void* stream, int64_t* stats, const float2* ext_table, int64_t* layer_stats = nullptr) {
+                    void* stream, int64_t* stats, const float2* ext_table, int64_t* layer_stats = nullptr,
+                    uint4* Cc = nullptr, const unsigned* colour = nullptr) {
     // F = 0: nothing to fuse, the frame arrays may be null (an empty tensor's pointer)
     SFMHIP_REQUIRE(D > 1 && H > 1 && W > 1 && F >= 0 && Hd > 0 && Wd > 0, "sfmhip_tsdf_integrate: bad shape");
     SFMHIP_REQUIRE(0 <= z0 && z0 <= z1 && z1 <= D, "sfmhip_tsdf_integrate: bad z range");
     SFMHIP_REQUIRE(trunc > 0.f, "sfmhip_tsdf_integrate: trunc must be > 0");
     if (F == 0 || z0 == z1) return SFMHIP_OK;
-    SFMHIP_REQUIRE(T && Wt && bmin && bmax && (F == 0 || (depth && poses && Kf)), "sfmhip_tsdf_integrate: null pointer");
+    // colour mode (Cc != nullptr, V7): the same passes, then tsdf_colour_kernel on Cc instead of
+    // tsdf_fuse_kernel on T / Wt (which are not touched and may be null)
+    SFMHIP_REQUIRE((Cc ? colour != nullptr : T && Wt) && bmin && bmax && (F == 0 || (depth && poses && Kf)),
+                   "sfmhip_tsdf_integrate: null pointer");
     SFMHIP_REQUIRE((int64_t)Hd * Wd * 4 < (int64_t)INT_MAX && Wd < (1 << 22) && Hd < (1 << 22),
                    "sfmhip_tsdf_integrate: depth map too large (4*Hd*Wd must be < 2^31)");
     for (int a = 0; a < 3; ++a)
@@ -1372,7 +1487,17 @@ static int tsdf_run(float* T, float* Wt, int D, int H, int W, int z0, int z1, co
         fc.nbv = nbv;
         fc.trunc = trunc;
         fc.inv_trunc = 1.0f / trunc;
-        if (deep)
+        if (Cc) {
+            const unsigned* cp = colour + (size_t)f0 * Hd * Wd;
+            if (deep)
+                hipLaunchKernelGGL((vox_test ? tsdf_colour_kernel<true, 4> : tsdf_colour_kernel<false, 4>),
+                                   dim3((unsigned)main_slots), dim3(256), 0, st, Cc, cp, D, H, W, z0, z1, fc, gb, nf, sm,
+                                   cmask, cfree, nw, ord);
+            else
+                hipLaunchKernelGGL((vox_test ? tsdf_colour_kernel<true, 2> : tsdf_colour_kernel<false, 2>),
+                                   dim3((unsigned)main_slots), dim3(256), 0, st, Cc, cp, D, H, W, z0, z1, fc, gb, nf, sm,
+                                   cmask, cfree, nw, ord);
+        } else if (deep)
             hipLaunchKernelGGL((vox_test ? tsdf_fuse_kernel<true, 4> : tsdf_fuse_kernel<false, 4>),
                                dim3((unsigned)main_slots), dim3(256), 0, st, T, Wt, D, H, W, z0, z1, fc, gb, nf, sm,
                                cmask, cfree, nw, ord);
@@ -1380,7 +1505,7 @@ static int tsdf_run(float* T, float* Wt, int D, int H, int W, int z0, int z1, co
             hipLaunchKernelGGL((vox_test ? tsdf_fuse_kernel<true, 2> : tsdf_fuse_kernel<false, 2>),
                                dim3((unsigned)main_slots), dim3(256), 0, st, T, Wt, D, H, W, z0, z1, fc, gb, nf, sm,
                                cmask, cfree, nw, ord);
-        rc = check_launch("tsdf_fuse_kernel");
+        rc = check_launch(Cc ? "tsdf_colour_kernel" : "tsdf_fuse_kernel");
         if (rc != SFMHIP_OK) break;
     }
     scratch_free(sc, st);
@@ -1406,6 +1531,19 @@ extern "C" int sfmhip_tsdf_integrate_tab(float* T, float* Wt, int D, int H, int 
     SFMHIP_REQUIRE(table || F == 0, "sfmhip_tsdf_integrate_tab: null pointer");
     return tsdf_run(T, Wt, D, H, W, z0, z1, depth, F, Hd, Wd, poses, Kf, bmin, bmax, trunc, stream, nullptr,
                     reinterpret_cast<const float2*>(table));
+}
+
+extern "C" int sfmhip_tsdf_integrate_colour(uint32_t* C, int D, int H, int W, int z0, int z1, const float* depth,
+                                            const uint8_t* colour, int F, int Hd, int Wd, const float* poses,
+                                            const float* Kf, const float* bmin, const float* bmax, float trunc,
+                                            const float* table, void* stream) {
+    SFMHIP_REQUIRE(C || F == 0 || z0 == z1, "sfmhip_tsdf_integrate_colour: null pointer");
+    // one voxel is one 128-bit access, one pixel one dword gather
+    SFMHIP_REQUIRE((reinterpret_cast<uintptr_t>(C) & 15u) == 0 && (reinterpret_cast<uintptr_t>(colour) & 3u) == 0,
+                   "sfmhip_tsdf_integrate_colour: C must be 16-byte and colour 4-byte aligned");
+    return tsdf_run(nullptr, nullptr, D, H, W, z0, z1, depth, F, Hd, Wd, poses, Kf, bmin, bmax, trunc, stream, nullptr,
+                    reinterpret_cast<const float2*>(table), nullptr, reinterpret_cast<uint4*>(C),
+                    reinterpret_cast<const unsigned*>(colour));
 }
 
 extern "C" int sfmhip_tsdf_block_table(const float* depth, int F, int Hd, int Wd, int f0, int f1, float* table,

@@ -227,3 +227,27 @@ def tsdf_scene(n_frames=257, Hd=IMG_H, Wd=IMG_W, focal=FOCAL, radius=4.0, seed=5
             best = torch.where(okp & (tp < best), tp, best)
             depth[f, r0:r0 + vs.shape[0]] = torch.where(torch.isfinite(best), best, torch.zeros_like(best))
     return depth, torch.from_numpy(poses).to(device), torch.from_numpy(K).to(device)
+
+
+def tsdf_scene_colour(depth, poses, K):
+    """Procedural colour images for depth maps like :func:`tsdf_scene`'s: every valid pixel
+    (depth > 0) is back-projected to its world hit point X and coloured
+    clip(rint(127.5 + 100 X), 0, 255), x, y, z -> r, g, b; invalid pixels are 0 and the
+    fourth byte is 255.  Returns (F,Hd,Wd,4) uint8 on depth's device (frame by frame)."""
+    depth = torch.as_tensor(depth)
+    device = depth.device
+    poses = torch.as_tensor(poses).to(device=device, dtype=torch.float64)
+    K = torch.as_tensor(K).to(device=device, dtype=torch.float64)
+    F, Hd, Wd = depth.shape
+    out = torch.zeros((F, Hd, Wd, 4), dtype=torch.uint8, device=device)
+    us = torch.arange(Wd, device=device, dtype=torch.float64)[None, :]
+    vs = torch.arange(Hd, device=device, dtype=torch.float64)[:, None]
+    for f in range(F):
+        d = depth[f].to(torch.float64)
+        fx, fy, cx, cy = (float(x) for x in K[f])
+        pc = torch.stack(torch.broadcast_tensors((us - cx) / fx * d, (vs - cy) / fy * d, d), -1)   # camera frame
+        X = (pc - poses[f, :, 3]) @ poses[f, :, :3]   # R^T (pc - t)
+        rgb = torch.clamp(torch.round(127.5 + 100.0 * X), 0, 255).to(torch.uint8)
+        out[f, ..., :3] = torch.where((d > 0)[..., None], rgb, torch.zeros_like(rgb))
+        out[f, ..., 3] = 255
+    return out

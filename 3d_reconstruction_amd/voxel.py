@@ -253,25 +253,74 @@ def tsdf_integrate(T: torch.Tensor, Wt: torch.Tensor, depth: torch.Tensor, poses
     z1 = D if z1 is None else int(z1)
     if not 0 <= int(z0) <= z1 <= D:
         raise ValueError(f"z-slab [{z0}, {z1}) outside [0, {D}]")
-    dp = dev(depth, torch.float32)
-    ps = dev(poses, torch.float32)
-    kk = dev(K, torch.float32)
-    if dp.dim() != 3:
-        raise ValueError(f"depth must be (F,Hd,Wd), got {tuple(dp.shape)}")
+    dp, ps, kk = _frame_args(depth, poses, K)
     F, Hd, Wd = dp.shape
-    if tuple(ps.shape) != (F, 3, 4):
-        raise ValueError(f"poses must be ({F},3,4) to match depth, got {tuple(ps.shape)}")
-    if tuple(kk.shape) != (F, 4):
-        raise ValueError(f"K must be ({F},4) to match depth, got {tuple(kk.shape)}")
     bmn, bmx = _f3(bmin), _f3(bmax)
     if block_table is None:
         call("sfmhip_tsdf_integrate", ptr(T), ptr(Wt), D, H, W, int(z0), z1, ptr(dp), F, Hd, Wd, ptr(ps), ptr(kk),
              _host_ptr(bmn), _host_ptr(bmx), float(trunc), stream_ptr())
         return
-    if tuple(block_table.shape) != block_table_shape(F, Hd, Wd) or block_table.dtype != torch.float32 or \
-            not block_table.is_contiguous() or block_table.device != T.device:
-        raise ValueError(f"block_table must be a contiguous float32 {block_table_shape(F, Hd, Wd)} tensor on {T.device}")
+    _check_block_table(block_table, F, Hd, Wd, T.device)
     call("sfmhip_tsdf_integrate_tab", ptr(T), ptr(Wt), D, H, W, int(z0), z1, ptr(dp), F, Hd, Wd, ptr(ps), ptr(kk),
+         _host_ptr(bmn), _host_ptr(bmx), float(trunc), ptr(block_table), stream_ptr())
+
+
+def _frame_args(depth, poses, K):
+    """The frame arrays of a TSDF call as contiguous f32 device tensors, shapes checked."""
+    dp = dev(depth, torch.float32)
+    ps = dev(poses, torch.float32)
+    kk = dev(K, torch.float32)
+    if dp.dim() != 3:
+        raise ValueError(f"depth must be (F,Hd,Wd), got {tuple(dp.shape)}")
+    F = dp.shape[0]
+    if tuple(ps.shape) != (F, 3, 4):
+        raise ValueError(f"poses must be ({F},3,4) to match depth, got {tuple(ps.shape)}")
+    if tuple(kk.shape) != (F, 4):
+        raise ValueError(f"K must be ({F},4) to match depth, got {tuple(kk.shape)}")
+    return dp, ps, kk
+
+
+def _check_block_table(block_table, F, Hd, Wd, device) -> None:
+    if tuple(block_table.shape) != block_table_shape(F, Hd, Wd) or block_table.dtype != torch.float32 or \
+            not block_table.is_contiguous() or block_table.device != device:
+        raise ValueError(f"block_table must be a contiguous float32 {block_table_shape(F, Hd, Wd)} tensor on {device}")
+
+
+def tsdf_integrate_colour(C: torch.Tensor, depth: torch.Tensor, colour: torch.Tensor, poses: torch.Tensor,
+                          K: torch.Tensor, bmin, bmax, trunc: float, z0: int = 0, z1: int | None = None,
+                          block_table: torch.Tensor | None = None) -> None:
+    """In-place colour fusion into z-slices [z0, z1) of C (D,H,W,4) int32: per voxel
+    {sum_r, sum_g, sum_b, n}, arithmetic modulo 2^32 (the V7 block of include/sfmhip.h).
+
+    depth, poses, K, bounds, trunc and block_table as for :func:`tsdf_integrate`; colour
+    (F,Hd,Wd,3) or (F,Hd,Wd,4) uint8, pixel-aligned with depth (r, g, b and an ignored
+    fourth byte).  A voxel takes a frame's colour iff :func:`tsdf_integrate` would update it
+    from that frame with tsdf < 1: it adds the r, g, b of the pixel the distance update read
+    and 1 to n.  Integer sums: any frame order, z-slab split or grouping of the frames into
+    calls gives the same bits, and C does not depend on T or Wt.  A channel sum can pass
+    2^31 only after 2^23 updates of one voxel.
+    :func:`tsdf_extract_surface` (``colours=C``) turns C into per-vertex colours."""
+    gpu = require_gpu()
+    if not isinstance(C, torch.Tensor) or C.dtype != torch.int32 or not C.is_contiguous() or C.dim() != 4 or \
+            C.shape[3] != 4:
+        raise ValueError("C must be a contiguous int32 (D,H,W,4) device tensor")
+    if C.device != gpu:
+        raise ValueError(f"C must live on the current HIP device {gpu}, got {C.device}")
+    D, H, W = C.shape[:3]
+    z1 = D if z1 is None else int(z1)
+    if not 0 <= int(z0) <= z1 <= D:
+        raise ValueError(f"z-slab [{z0}, {z1}) outside [0, {D}]")
+    dp, ps, kk = _frame_args(depth, poses, K)
+    F, Hd, Wd = dp.shape
+    col = dev(colour, torch.uint8)
+    if col.dim() != 4 or tuple(col.shape[:3]) != (F, Hd, Wd) or col.shape[3] not in (3, 4):
+        raise ValueError(f"colour must be ({F},{Hd},{Wd},3|4) uint8 to match depth, got {tuple(col.shape)}")
+    if col.shape[3] == 3:   # one dword per pixel
+        col = torch.nn.functional.pad(col, (0, 1))
+    bmn, bmx = _f3(bmin), _f3(bmax)
+    if block_table is not None:
+        _check_block_table(block_table, F, Hd, Wd, C.device)
+    call("sfmhip_tsdf_integrate_colour", ptr(C), D, H, W, int(z0), z1, ptr(dp), ptr(col), F, Hd, Wd, ptr(ps), ptr(kk),
          _host_ptr(bmn), _host_ptr(bmx), float(trunc), ptr(block_table), stream_ptr())
 
 
@@ -344,7 +393,8 @@ def tsdf_cull_stats(shape, depth: torch.Tensor, poses: torch.Tensor, K: torch.Te
 
 
 def tsdf_extract_surface(T: torch.Tensor, Wt: torch.Tensor, bmin, bmax, iso: float = 0.0, min_weight: float = 1.0,
-                         z0: int = 0, z1: int | None = None, normals: bool = True):
+                         z0: int = 0, z1: int | None = None, normals: bool = True,
+                         colours: torch.Tensor | None = None):
     """Triangle mesh of the iso-surface of a fused TSDF grid (marching tetrahedra on the
     Kuhn 6-tetrahedron split; the semantics are the V6 block of include/sfmhip.h).
 
@@ -356,7 +406,12 @@ def tsdf_extract_surface(T: torch.Tensor, Wt: torch.Tensor, bmin, bmax, iso: flo
 
     Returns device tensors ``(vertices (V,3) f32, normals (V,3) f32 | None, faces (F,3)
     int32)``: a consistently oriented mesh, normals and face orientation towards free
-    space (increasing T).  D, H or W of 1, or z0 == z1, gives empty (0,3) outputs."""
+    space (increasing T).  D, H or W of 1, or z0 == z1, gives empty (0,3) outputs.
+
+    ``colours``: the (D,H,W,4) int32 grid of :func:`tsdf_integrate_colour`; the call then
+    returns a fourth tensor ``vertex_colours (V,4) uint8`` (r, g, b, alpha; the V7 block of
+    include/sfmhip.h): each vertex the interpolation of its edge's two voxel colours, alpha 0
+    where neither endpoint ever took a colour sample."""
     gpu = require_gpu()
     if not isinstance(T, torch.Tensor) or not isinstance(Wt, torch.Tensor):
         raise ValueError("T and Wt must be torch tensors")
@@ -368,6 +423,12 @@ def tsdf_extract_surface(T: torch.Tensor, Wt: torch.Tensor, bmin, bmax, iso: flo
     if T.device != gpu or Wt.device != gpu:
         raise ValueError(f"T and Wt must live on the current HIP device {gpu}, got {T.device} / {Wt.device}")
     D, H, W = T.shape
+    if colours is not None:
+        if not isinstance(colours, torch.Tensor) or colours.dtype != torch.int32 or not colours.is_contiguous() or \
+                tuple(colours.shape) != (D, H, W, 4):
+            raise ValueError(f"colours must be a contiguous int32 {(D, H, W, 4)} device tensor")
+        if colours.device != gpu:
+            raise ValueError(f"colours must live on the current HIP device {gpu}, got {colours.device}")
     if min(D, H, W) < 1:
         raise ValueError(f"empty grid {tuple(T.shape)}")
     z0 = int(z0)
@@ -396,4 +457,9 @@ def tsdf_extract_surface(T: torch.Tensor, Wt: torch.Tensor, bmin, bmax, iso: flo
     faces = torch.empty((ntri, 3), dtype=torch.int32, device=gpu)
     call("sfmhip_tsdf_surface_emit", *head, _host_ptr(bmn), _host_ptr(bmx), ptr(edge_mask), ptr(vert_off),
          ptr(tri_off), ptr(vertices), ptr(nrm), ptr(faces), stream_ptr())
-    return vertices, nrm, faces
+    if colours is None:
+        return vertices, nrm, faces
+    rgba = torch.empty((nvert, 4), dtype=torch.uint8, device=gpu)
+    call("sfmhip_tsdf_surface_colours", ptr(T), ptr(Wt), ptr(colours), D, H, W, z0, z1, float(iso), float(min_weight),
+         ptr(edge_mask), ptr(vert_off), ptr(rgba), stream_ptr())
+    return vertices, nrm, faces, rgba

@@ -432,6 +432,49 @@ int sfmhip_tsdf_surface_emit(const float* T, const float* Wt, int D, int H, int 
                              const uint8_t* edge_mask, const int32_t* vert_off, const int32_t* tri_off,
                              float* vertices, float* normals /* nullable */, int32_t* faces, void* stream);
 
+/* ---- V7: TSDF colour fusion (build-defined) --------------------------------
+ * Image colour fused beside the distance of V5 and interpolated onto the
+ * vertices of V6: the reference's final artefact is a coloured .ply
+ * (sfm.py:54-77, numpy2ply.py: xyz + colour).  Restated in numpy by
+ * tests/tsdf_colour_ref.py.
+ *
+ * State: C (D,H,W,4) i32, read and written as u32 with arithmetic modulo 2^32:
+ * per voxel {sum_r, sum_g, sum_b, n}, 16 bytes, 16-byte aligned (one 128-bit
+ * access per voxel).  A channel sum can pass 2^31 only after 2^23 updates of
+ * one voxel (255 * 2^23 < 2^31); n and the sums wrap modulo 2^32 beyond.
+ *
+ * Input: colour [F][Hd][Wd][4] u8, bytes r, g, b, x (x ignored), pixel-aligned
+ * with depth: pixel (v,u) is the dword at the depth gather's own offset.
+ *
+ * Rule per (voxel, frame): V5 exactly as oracle/voxel.py _tsdf_frames writes
+ * it (the same f32 operations in the same order: the frame-skip rule,
+ * 2^-60 <= Zc < 2^60, iz = 1/Zc, pixel = floor((fx Xc) iz + (cx + 0.5)),
+ * off-image, depth > 0, sdf = depth - Zc, skip sdf < -mu,
+ * ts = min(1, sdf (1/mu))).  The voxel takes the frame's colour iff V5 would
+ * update it AND ts < 1 (f32 compare): sums += (r, g, b) of that pixel, n += 1.
+ * Nothing else: no 512-frame steps, no dependence on T or Wt, and integer sums,
+ * so any frame order, any z-slab split and any grouping of the frames into
+ * calls give the same bits.  F = 0 or z0 = z1: a no-op.  table: nullable, the
+ * caller's block table as for sfmhip_tsdf_integrate_tab (same bits).
+ *
+ * Vertex colour of an active edge (v,k) of V6 with endpoints v, v+o and V6's
+ * own s: per channel col(u) = f32(sum[u]) / f32(n[u]) where n[u] > 0 (u32 ->
+ * f32 round-to-nearest, IEEE f32 division); both endpoints coloured:
+ * m = a + s (b - a), no FMA; one coloured: m = its col; neither: m = 0 and
+ * alpha = 0.  Byte = rint(min(255, max(0, m))), round-half-even; alpha = 255
+ * when at least one endpoint is coloured.  rgba [V][4] u8 in vertex order
+ * (edge_mask / vert_off as sfmhip_tsdf_surface_count left them for the same
+ * grids, range, iso and min_weight); may be null when V = 0.                 */
+int sfmhip_tsdf_integrate_colour(uint32_t* C, int D, int H, int W, int z0, int z1,
+                                 const float* depth, const uint8_t* colour, int F, int Hd, int Wd,
+                                 const float* poses, const float* Kf,
+                                 const float* bmin, const float* bmax, float trunc,
+                                 const float* table /* nullable */, void* stream);
+int sfmhip_tsdf_surface_colours(const float* T, const float* Wt, const uint32_t* C,
+                                int D, int H, int W, int z0, int z1, float iso, float min_weight,
+                                const uint8_t* edge_mask, const int32_t* vert_off,
+                                uint8_t* rgba /* [V][4] */, void* stream);
+
 /* ---- §8f row 2: geometric verification (batched over image pairs) --------
  * cv2.findEssentialMat(pts0, pts1, K, method=cv2.RANSAC, prob=0.999,
  * threshold=1) at matching.py:134 and sfm.py:108 (OpenCV five-point.cpp +
