@@ -163,6 +163,7 @@ static Knobs read_knobs() {
     k.dlt_qr = env_knob("SFMHIP_DLT_QR", 0);
     k.render_sort = env_knob("SFMHIP_RENDER_SORT", 1);
     k.dda_direct = env_knob("SFMHIP_DDA_DIRECT", -1);
+    k.raycast_skip = env_knob("SFMHIP_RAYCAST_SKIP", 1);
     k.ab = env_knob("SFMHIP_AB", 0);
     return k;
 }
@@ -187,6 +188,7 @@ extern "C" int sfmhip_knobs_reload(void) {
     return SFMHIP_OK;
 }
 
+// 0.3.0 also carries sfmhip_tsdf_raycast (V8), added without a version step: no older entry point changed
 // 0.3.0: sfmhip_match_pairs_i16 / sfmhip_match_pairs_exact_i16 (the int16 graph written by the kernels)
 // 0.2.0: sfmhip_ba_solve takes n_obs (between n_pairs and ftol); sfmhip_scratch_release_stream
 extern "C" int sfmhip_version(void) { return (0 << 16) | (3 << 8) | 0; }

@@ -463,3 +463,102 @@ def tsdf_extract_surface(T: torch.Tensor, Wt: torch.Tensor, bmin, bmax, iso: flo
     call("sfmhip_tsdf_surface_colours", ptr(T), ptr(Wt), ptr(colours), D, H, W, z0, z1, float(iso), float(min_weight),
          ptr(edge_mask), ptr(vert_off), ptr(rgba), stream_ptr())
     return vertices, nrm, faces, rgba
+
+
+def tsdf_raycast(T: torch.Tensor, Wt: torch.Tensor, poses: torch.Tensor, K: torch.Tensor, size, bmin, bmax,
+                 iso: float = 0.0, min_weight: float = 1.0, near: float = 0.0, far: float | None = None,
+                 step: float | None = None, normals: bool = False, colours: torch.Tensor | None = None,
+                 steps: bool = False):
+    """Ray-cast a fused TSDF grid into the depth, normal and colour maps it predicts for V
+    cameras (the semantics are the V8 block of include/sfmhip.h).
+
+    T, Wt: (D,H,W) contiguous f32 device tensors as :func:`tsdf_integrate` leaves them; poses
+    (V,3,4) world->camera and K (V,4) [fx, fy, cx, cy] as for :func:`tsdf_integrate`;
+    ``size`` = (Hd, Wd), pixel centres at integer coordinates.  Each pixel's ray is marched
+    in camera depth: samples at Zc = near + k * step, k = 0 .. n_samples-1 with
+    ``n_samples = floor((far - near) / step) + 1`` (at most 65536), trilinear T at each, and
+    the first front-face crossing (T >= iso, then T < iso, both samples in cells whose 8
+    corners are observed: ``Wt >= min_weight`` and T finite) gives the depth by linear
+    interpolation; 0 where there is none, :func:`tsdf_integrate`'s "invalid" value, so the
+    depth map can be integrated again as it is.
+
+    ``step`` defaults to half the smallest voxel edge, ``far`` to the largest camera depth
+    of a corner of the grid box over the views.  The ray direction is not normalised: the
+    spacing of the samples along a ray is ``step * |dc|`` with dc = ((u - cx)/fx,
+    (v - cy)/fy, 1), larger towards the image corners.  Keep ``step * |dc|`` under the
+    truncation distance of the fusion, or a ray can step over the band around the surface.
+
+    Returns device tensors ``(depth (V,Hd,Wd) f32, normals (V,Hd,Wd,3) f32 | None, rgba
+    (V,Hd,Wd,4) uint8 | None)``: unit world-frame normals towards increasing T (free space)
+    when ``normals``; r, g, b, alpha from ``colours``, the (D,H,W,4) int32 grid of
+    :func:`tsdf_integrate_colour` (alpha 0 where no corner of the hit cell ever took a colour
+    sample).  ``steps=True`` appends an int32 (V,Hd,Wd) count of the samples the kernel
+    evaluated per pixel (a diagnostic of the empty-space skipping, SFMHIP_RAYCAST_SKIP).
+    A view with a non-finite (or >= 2^60) pose or intrinsic entry, or fx or fy of 0, gives
+    all-zero maps."""
+    gpu = require_gpu()
+    if not isinstance(T, torch.Tensor) or not isinstance(Wt, torch.Tensor):
+        raise ValueError("T and Wt must be torch tensors")
+    if T.dtype != torch.float32 or Wt.dtype != torch.float32 or not T.is_contiguous() or not Wt.is_contiguous():
+        raise ValueError("T and Wt must be contiguous float32 device tensors")
+    if T.dim() != 3 or tuple(Wt.shape) != tuple(T.shape):
+        raise ValueError(f"T and Wt must be (D,H,W) tensors of one shape, got {tuple(T.shape)} and "
+                         f"{tuple(Wt.shape)}")
+    if T.device != gpu or Wt.device != gpu:
+        raise ValueError(f"T and Wt must live on the current HIP device {gpu}, got {T.device} / {Wt.device}")
+    D, H, W = T.shape
+    if min(D, H, W) < 2:
+        raise ValueError(f"the grid needs at least 2 voxels per axis, got {tuple(T.shape)}")
+    if colours is not None:
+        if not isinstance(colours, torch.Tensor) or colours.dtype != torch.int32 or not colours.is_contiguous() or \
+                tuple(colours.shape) != (D, H, W, 4):
+            raise ValueError(f"colours must be a contiguous int32 {(D, H, W, 4)} device tensor")
+        if colours.device != gpu:
+            raise ValueError(f"colours must live on the current HIP device {gpu}, got {colours.device}")
+    ps = dev(poses, torch.float32)
+    kk = dev(K, torch.float32)
+    if ps.dim() != 3 or tuple(ps.shape[1:]) != (3, 4):
+        raise ValueError(f"poses must be (V,3,4), got {tuple(ps.shape)}")
+    V = ps.shape[0]
+    if tuple(kk.shape) != (V, 4):
+        raise ValueError(f"K must be ({V},4) to match poses, got {tuple(kk.shape)}")
+    if np.size(size) != 2:
+        raise ValueError(f"size must be (Hd, Wd), got {size}")
+    Hd, Wd = (int(v) for v in size)
+    if Hd < 0 or Wd < 0:
+        raise ValueError(f"size must be non-negative, got {size}")
+    if not float(min_weight) > 0.0:
+        raise ValueError(f"min_weight must be > 0, got {min_weight}")
+    for name, b in (("bmin", bmin), ("bmax", bmax)):
+        if np.size(b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else b) not in (1, 3):
+            raise ValueError(f"{name} must have 1 or 3 components")
+    bmn, bmx = _f3(bmin), _f3(bmax)
+    lo, hi = bmn.astype(np.float64), bmx.astype(np.float64)
+    if not (hi > lo).all():
+        raise ValueError(f"bmax must be above bmin on every axis, got {bmin} / {bmax}")
+    if step is None:
+        step = 0.5 * float(((hi - lo) / np.array([W - 1, H - 1, D - 1], np.float64)).min())
+    near, step = float(near), float(step)
+    if not (near >= 0.0 and np.isfinite(near)):
+        raise ValueError(f"near must be finite and >= 0, got {near}")
+    if not (step > 0.0 and np.isfinite(step)):
+        raise ValueError(f"step must be finite and > 0, got {step}")
+    if far is None:   # the deepest corner of the grid box over the views (host)
+        corners = np.array([[x, y, z, 1.0] for x in (lo[0], hi[0]) for y in (lo[1], hi[1]) for z in (lo[2], hi[2])])
+        zc = ps[:, 2, :].detach().cpu().numpy().astype(np.float64) @ corners.T
+        zc = zc[np.isfinite(zc)]
+        far = float(zc.max()) if zc.size else near
+    far = float(far)
+    if not np.isfinite(far):
+        raise ValueError(f"far must be finite, got {far}")
+    n_samples = max(int(np.floor((far - near) / step)) + 1, 1)
+    if n_samples > 65536:
+        raise ValueError(f"{n_samples} samples per ray (far {far}, near {near}, step {step}); at most 65536")
+    depth = torch.empty((V, Hd, Wd), dtype=torch.float32, device=gpu)
+    nrm = torch.empty((V, Hd, Wd, 3), dtype=torch.float32, device=gpu) if normals else None
+    rgba = torch.empty((V, Hd, Wd, 4), dtype=torch.uint8, device=gpu) if colours is not None else None
+    cnt = torch.empty((V, Hd, Wd), dtype=torch.int32, device=gpu) if steps else None
+    call("sfmhip_tsdf_raycast", ptr(T), ptr(Wt), ptr(colours), D, H, W, ptr(ps), ptr(kk), V, Hd, Wd,
+         _host_ptr(bmn), _host_ptr(bmx), float(iso), float(min_weight), near, step, n_samples, ptr(depth), ptr(nrm),
+         ptr(rgba), ptr(cnt), stream_ptr())
+    return (depth, nrm, rgba, cnt) if steps else (depth, nrm, rgba)

@@ -475,6 +475,93 @@ int sfmhip_tsdf_surface_colours(const float* T, const float* Wt, const uint32_t*
                                 const uint8_t* edge_mask, const int32_t* vert_off,
                                 uint8_t* rgba /* [V][4] */, void* stream);
 
+/* ---- V8: ray-cast of the fused TSDF grid (build-defined) -------------------
+ * The depth map, normal map and colour image the fused model (T, Wt[, C])
+ * predicts for V cameras: the third member of integrate / extract / ray-cast.
+ * The reference has no counterpart (its sdf.py composites a learned SDF, V4).
+ * Restated in numpy by tests/tsdf_raycast_ref.py.  Every f32 operation is one
+ * IEEE round-to-nearest step in the order written, no FMA.
+ *
+ * Inputs: T, Wt (D,H,W) f32 as sfmhip_tsdf_integrate leaves them (D, H, W >= 2,
+ * D*H*W < 2^31); C (D,H,W,4) u32 as V7 leaves it (nullable; 16-byte aligned);
+ * poses [V][3][4] world->camera and Kf [V][4] = fx, fy, cx, cy (device f32);
+ * image size Hd x Wd; HOST float[3] bmin / bmax (finite, |.| < 2^60, every
+ * s_a = (bmax_a - bmin_a)/f32(R_a - 1) > 0; R = (W, H, D) for a = x, y, z); iso;
+ * min_weight (<= 0 is SFMHIP_E_ARG); t_near >= 0, step > 0 (both finite) and
+ * 1 <= n_samples <= 65536 (else SFMHIP_E_ARG).  V, Hd or Wd of 0: a no-op.
+ * The call covers the whole grid: there is no z-range (a hit needs both samples
+ * of a pair in the caller's grid; shard by views on a replicated grid).
+ *
+ * View skip rule (V5's): a view with a non-finite pose or intrinsic entry, or one
+ * of magnitude >= 2^60, or with fx == 0 or fy == 0, gives all-zero outputs.
+ *
+ * Ray of pixel (v,u), pixel centres at integer coordinates (V5's convention);
+ * Rra = poses[r][a], t_r = poses[r][3]:
+ *   dc_x = (f32(u) - cx)/fx;  dc_y = (f32(v) - cy)/fy;  (dc_z = 1)
+ *   o_a  = -((R0a t0 + R1a t1) + R2a t2)
+ *   dw_a = (R0a dc_x + R1a dc_y) + R2a
+ * The direction is not normalised: the ray parameter is the camera depth Zc.
+ *
+ * Point at parameter t:  p_a = o_a + t dw_a;  g_a = (p_a - bmin_a)/s_a;
+ * i_a = floor(g_a);  f_a = g_a - i_a.  Its cell is IN RANGE iff
+ * 0 <= i_a <= R_a - 2 on all three axes (a NaN fails) and VALID iff it is in
+ * range and the 8 corner voxels (z,y,x) + {0,1}^3 are observed in V6's sense
+ * (Wt >= min_weight and T finite).
+ * Samples: t_k = t_near + f32(k) step, k = 0 .. n_samples-1 (no running sum).
+ * F(k), for a VALID sample, with lerp(a,b,w) = a + w (b - a), Tzyx the corners:
+ *   a_zy = lerp(T_zy0, T_zy1, f_x);  b_z = lerp(a_z0, a_z1, f_y);
+ *   F = lerp(b_0, b_1, f_z).
+ *
+ * Hit: the smallest k in [1, n_samples) with samples k-1 and k both VALID,
+ * F(k-1) >= iso and F(k) < iso: a front-face crossing (V6: inside(v) is
+ * T < iso).  Back-face crossings and pairs with an invalid member are ignored
+ * and the march goes on.  (A NaN F of a valid sample, from inf - inf of huge
+ * finite corners, fails both comparisons.)
+ *   depth = t_{k-1} + step ((F(k-1) - iso)/(F(k-1) - F(k)));  no hit: depth = 0,
+ * V5's "invalid" value, so depth feeds sfmhip_tsdf_integrate as it is.
+ *
+ * Normal (nullable output, world frame) and colour (nullable, needs C) are taken
+ * at p* = o + depth dw in p*'s own cell (i, f) by the rules above; both are all
+ * zero when there is no hit or that cell is not VALID.
+ *   Normal: the gradient of the cell's trilinear interpolant,
+ *     x: d_zy = T_zy1 - T_zy0;  gx = lerp(lerp(d_00, d_01, f_y), lerp(d_10, d_11, f_y), f_z)/s_x
+ *     y: d_zx = T_z1x - T_z0x;  gy = lerp(lerp(d_00, d_01, f_x), lerp(d_10, d_11, f_x), f_z)/s_y
+ *     z: d_yx = T_1yx - T_0yx;  gz = lerp(lerp(d_00, d_01, f_x), lerp(d_10, d_11, f_x), f_y)/s_z
+ *   len = sqrt((gx gx + gy gy) + gz gz); n = g/len, (0,0,0) when len is 0 or not
+ *   finite.  It points towards increasing T, as V6's normals do.
+ *   Colour: corner c = dx + 2 dy + 4 dz has weight w_c = (ux uy) uz with
+ *   u_a = f_a where the corner's offset on axis a is 1, else 1 - f_a, and V7's mean
+ *   col_c = f32(sum)/f32(n).  Starting from 0 and adding in ascending c over the
+ *   corners with n > 0: num += w_c col_c (per channel), den += w_c; m = num/den;
+ *   byte = rint(fmin(255, fmax(0, m))) half-even (fmin/fmax return the other
+ *   operand for a NaN, so 0/0 gives 0), alpha 255.  No corner with n > 0:
+ *   (0,0,0,0).
+ *
+ * Outputs (device): depth [V][Hd][Wd] f32; normals [V][Hd][Wd][3] f32; rgba
+ * [V][Hd][Wd][4] u8 (4-byte aligned); steps [V][Hd][Wd] i32 (nullable,
+ * diagnostic, outside the bit-exact contract): the number of samples whose F the
+ * kernel evaluated for the pixel.
+ *
+ * Skipping (SFMHIP_RAYCAST_SKIP, default 1; 0 evaluates every sample of every
+ * ray up to its hit): the kernel leaves out only samples it has proved cannot be
+ * the k of a hit, and evaluates F(k-1) for the first k it keeps, so the outputs
+ * are the plain march's bit for bit.  The proofs: (1) every operation from k to
+ * i_a is monotone in k for a fixed ray, so i_a(k) is monotone and two samples in
+ * one brick of 8^3 cells, or both outside the grid on the same side of one axis,
+ * enclose only samples of that kind; (2) a valid sample whose cell origin lies in
+ * a brick has its corners among the brick's voxels dilated by one (up), and with
+ * L their minimum over the observed ones and A their largest magnitude,
+ * A < 2^126, three nested lerps give F >= L - 20 2^-24 A - 2^-140 or NaN (each
+ * lerp errs by at most 5.1 2^-24 max(|a|,|b|) + 2^-149 and the exact one stays in
+ * [a,b]); a brick with L >= iso + (2^-19 A + 2^-126), or with no observed voxel,
+ * cannot hold a sample with F < iso.  DESIGN.md K4d has the argument in full.   */
+int sfmhip_tsdf_raycast(const float* T, const float* Wt, const uint32_t* C /* nullable */,
+                        int D, int H, int W, const float* poses, const float* Kf, int V, int Hd, int Wd,
+                        const float* bmin, const float* bmax, float iso, float min_weight,
+                        float t_near, float step, int n_samples, float* depth,
+                        float* normals /* nullable */, uint8_t* rgba /* nullable */,
+                        int32_t* steps /* nullable */, void* stream);
+
 /* ---- §8f row 2: geometric verification (batched over image pairs) --------
  * cv2.findEssentialMat(pts0, pts1, K, method=cv2.RANSAC, prob=0.999,
  * threshold=1) at matching.py:134 and sfm.py:108 (OpenCV five-point.cpp +
