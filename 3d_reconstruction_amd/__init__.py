@@ -17,9 +17,9 @@ from .geometry import (Rodrigues, ba_sparse, calculate_reprojection_error,  # no
                        convertPointsFromHomogeneous, fd_jacobian, projectPoints,
                        residual_jacobian_batched, triangulatePoints, triangulate_batched, ba_solve_batched,
                        least_squares_ba)
-from .voxel import (MASK_PLENOXEL, MASK_SDF, VoxelGrid, tsdf_block_table, tsdf_cull_stats, tsdf_integrate,  # noqa: F401,E501
-                    tsdf_extract_surface, tsdf_integrate_colour, tsdf_layer_cost, tsdf_layer_stats, tsdf_raycast,
-                    voxel_traversal)
+from .voxel import (MASK_PLENOXEL, MASK_SDF, VoxelGrid, icp_normal_equations, icp_track, tsdf_block_table,  # noqa: F401,E501
+                    tsdf_cull_stats, tsdf_integrate, tsdf_extract_surface, tsdf_integrate_colour, tsdf_layer_cost,
+                    tsdf_layer_stats, tsdf_raycast, tsdf_track, voxel_traversal)
 from . import bow, mesh, pipeline, reconstruct, tracks, verify  # noqa: F401,E402
 from .mesh import write_ply  # noqa: F401
 from .bow import kmeans  # noqa: F401

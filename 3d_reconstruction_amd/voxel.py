@@ -15,6 +15,9 @@
   out like the ``sdf.py`` grid (build-defined).
 * :func:`tsdf_extract_surface` — the fused grid's iso-surface as a triangle mesh
   (marching tetrahedra, build-defined; ``mesh.write_ply`` stores it).
+* :func:`tsdf_raycast` — the depth, normal and colour maps the fused grid predicts.
+* :func:`icp_normal_equations`, :func:`icp_track`, :func:`tsdf_track` — frame-to-model
+  camera tracking by point-to-plane ICP against the ray-cast maps (build-defined).
 """
 from __future__ import annotations
 
@@ -562,3 +565,120 @@ def tsdf_raycast(T: torch.Tensor, Wt: torch.Tensor, poses: torch.Tensor, K: torc
          _host_ptr(bmn), _host_ptr(bmx), float(iso), float(min_weight), near, step, n_samples, ptr(depth), ptr(nrm),
          ptr(rgba), ptr(cnt), stream_ptr())
     return (depth, nrm, rgba, cnt) if steps else (depth, nrm, rgba)
+
+
+def _icp_args(depth, K, poses, model_depth, model_normals, model_poses, model_K, dist_max, cos_min):
+    """The arrays of an ICP call as contiguous f32 device tensors, shapes and gates checked."""
+    dp, ps, kk = _frame_args(depth, poses, K)
+    B = dp.shape[0]
+    md = dev(model_depth, torch.float32)
+    mn = dev(model_normals, torch.float32)
+    mp = dev(model_poses, torch.float32)
+    mk = dev(model_K, torch.float32)
+    if md.dim() != 3 or md.shape[0] != B:
+        raise ValueError(f"model_depth must be ({B},Hm,Wm) to match depth, got {tuple(md.shape)}")
+    if tuple(mn.shape) != tuple(md.shape) + (3,):
+        raise ValueError(f"model_normals must be {tuple(md.shape) + (3,)} to match model_depth, got {tuple(mn.shape)}")
+    if tuple(mp.shape) != (B, 3, 4):
+        raise ValueError(f"model_poses must be ({B},3,4) to match depth, got {tuple(mp.shape)}")
+    if tuple(mk.shape) != (B, 4):
+        raise ValueError(f"model_K must be ({B},4) to match depth, got {tuple(mk.shape)}")
+    dist_max = float(dist_max)
+    if not (dist_max > 0.0 and np.isfinite(dist_max)):
+        raise ValueError(f"dist_max must be finite and > 0, got {dist_max}")
+    dist2 = float(np.float32(dist_max) * np.float32(dist_max))
+    if not dist2 > 0.0:
+        raise ValueError(f"dist_max squared underflows in float32, got {dist_max}")
+    if cos_min is None:
+        cos2 = -1.0
+    else:
+        cos_min = float(cos_min)
+        if not 0.0 <= cos_min < 1.0:
+            raise ValueError(f"cos_min must be in [0, 1) or None, got {cos_min}")
+        cos2 = float(np.float32(cos_min) * np.float32(cos_min))
+    return dp, kk, ps, md, mn, mp, mk, dist2, cos2
+
+
+def icp_normal_equations(depth, K, poses, model_depth, model_normals, model_poses, model_K, dist_max: float,
+                         cos_min: float | None = None, mask: bool = False):
+    """One point-to-plane linearisation of B depth frames against model maps (the semantics
+    are the V9 block of include/sfmhip.h).
+
+    depth (B,Hf,Wf) f32 with K (B,4) [fx, fy, cx, cy] and the current estimates poses
+    (B,3,4) world->camera; model_depth (B,Hm,Wm) and model_normals (B,Hm,Wm,3) as
+    :func:`tsdf_raycast` returns them for the cameras model_poses / model_K.  A frame pixel is
+    paired with the model pixel it projects to and kept when the two points are within
+    ``dist_max`` (the gate is ``|e|^2 <= f32(dist_max)^2``) and, unless ``cos_min`` is None,
+    the frame's own normal (from its right and lower neighbours) makes an angle with the model
+    normal whose cosine is at least ``cos_min`` (in [0, 1)).
+
+    Returns ``sums`` (B,29) f64 on the device: the upper triangle of A = sum J J^T row-major
+    (21), g = sum J r (6), E = sum r^2 and the pair count n, with J = (pw x n, n) and
+    r = n . (pw - vmod); bit-reproducible from run to run.  ``mask=True`` appends the (B,Hf,Wf)
+    uint8 mask of the accepted pixels."""
+    gpu = require_gpu()
+    dp, kk, ps, md, mn, mp, mk, dist2, cos2 = _icp_args(depth, K, poses, model_depth, model_normals, model_poses,
+                                                         model_K, dist_max, cos_min)
+    B, Hf, Wf = dp.shape
+    sums = torch.zeros((B, 29), dtype=torch.float64, device=gpu)
+    msk = torch.zeros((B, Hf, Wf), dtype=torch.uint8, device=gpu) if mask else None
+    call("sfmhip_icp_normal_equations", ptr(dp), ptr(kk), ptr(ps), B, Hf, Wf, ptr(md), ptr(mn), ptr(mp), ptr(mk),
+         md.shape[1], md.shape[2], dist2, cos2, ptr(sums), ptr(msk), stream_ptr())
+    torch.cuda.current_stream().synchronize()
+    return (sums, msk) if mask else sums
+
+
+def icp_track(depth, K, poses0, model_depth, model_normals, model_poses, model_K, dist_max: float,
+              cos_min: float | None = None, iters: int = 10, min_pairs: int = 64, log: bool = False):
+    """Frame-to-model tracking: ``iters`` Gauss-Newton iterations of point-to-plane ICP from
+    ``poses0``, all on the device (two kernel launches per iteration, no host round trip).
+    Arguments as for :func:`icp_normal_equations`.
+
+    A view is lost when an iteration finds fewer than ``min_pairs`` (>= 6) pairs or a singular
+    system (an LDL^T pivot <= 1e-12 trace(A)): it keeps the pose it had, bit for bit, and its
+    later iterations do nothing.  A view with a non-finite camera is lost at once.  A frame
+    with no pixels loses every view.
+
+    Returns ``poses`` (B,3,4) f32 and ``lost`` (B,) bool on the device; ``log=True`` appends
+    the (B,iters,36) f64 record of every iteration: the 29 sums at its start, the 6 delta =
+    (omega, v) it applied, and its status (0 ok, 1 lost, 2 skipped view)."""
+    gpu = require_gpu()
+    dp, kk, ps, md, mn, mp, mk, dist2, cos2 = _icp_args(depth, K, poses0, model_depth, model_normals, model_poses,
+                                                         model_K, dist_max, cos_min)
+    iters, min_pairs = int(iters), int(min_pairs)
+    if iters < 0:
+        raise ValueError(f"iters must be >= 0, got {iters}")
+    if min_pairs < 6:
+        raise ValueError(f"min_pairs must be at least 6, got {min_pairs}")
+    B, Hf, Wf = dp.shape
+    out = ps.clone()
+    rec = torch.zeros((B, iters, 36), dtype=torch.float64, device=gpu)
+    if Hf * Wf == 0:
+        rec[:, :, 35] = 1.0
+    call("sfmhip_icp_track", ptr(dp), ptr(kk), B, Hf, Wf, ptr(md), ptr(mn), ptr(mp), ptr(mk), md.shape[1],
+         md.shape[2], dist2, cos2, iters, min_pairs, ptr(out), ptr(rec), stream_ptr())
+    torch.cuda.current_stream().synchronize()
+    if iters > 0:
+        lost = rec[:, -1, 35] != 0.0
+    else:
+        lost = torch.zeros((B,), dtype=torch.bool, device=gpu)
+    return (out, lost, rec) if log else (out, lost)
+
+
+def tsdf_track(T: torch.Tensor, Wt: torch.Tensor, depth, K, poses0, bmin, bmax, dist_max: float,
+               cos_min: float | None = None, iters: int = 10, min_pairs: int = 64, iso: float = 0.0,
+               min_weight: float = 1.0, near: float = 0.0, far: float | None = None, step: float | None = None,
+               log: bool = False):
+    """Track B depth frames against the fused grid (T, Wt): the model is ray-cast once, at
+    ``poses0`` with the frames' own ``K`` and image size (``tsdf_raycast(T, Wt, poses0, K,
+    (Hf, Wf), bmin, bmax, iso, min_weight, near, far, step, normals=True)``, so ``step``
+    defaults to half the smallest voxel edge and ``far`` to the deepest corner of the grid
+    box), and :func:`icp_track` aligns the frames to those maps.  Returns what
+    :func:`icp_track` returns; the poses feed :func:`tsdf_integrate` as they are.
+
+    For a coarse level, ray-cast at a smaller size yourself and call :func:`icp_track` with a
+    sub-sampled frame and K scaled to match."""
+    dp, ps, kk = _frame_args(depth, poses0, K)
+    md, mn, _ = tsdf_raycast(T, Wt, ps, kk, tuple(dp.shape[1:]), bmin, bmax, iso=iso, min_weight=min_weight, near=near,
+                             far=far, step=step, normals=True)
+    return icp_track(dp, kk, ps, md, mn, ps, kk, dist_max, cos_min=cos_min, iters=iters, min_pairs=min_pairs, log=log)

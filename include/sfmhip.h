@@ -562,6 +562,100 @@ int sfmhip_tsdf_raycast(const float* T, const float* Wt, const uint32_t* C /* nu
                         float* normals /* nullable */, uint8_t* rgba /* nullable */,
                         int32_t* steps /* nullable */, void* stream);
 
+/* ---- V9: frame-to-model tracking, point-to-plane ICP (build-defined) --------
+ * Aligns a depth frame against the maps V8 renders of the model the frame is
+ * about to be fused into: ray-cast, track, integrate is a closed loop on the
+ * device.  The reference has no counterpart.  Restated in numpy by
+ * tests/tsdf_track_ref.py.  Every f32 operation is one IEEE round-to-nearest step
+ * in the order written, no FMA.  It uses V5's projection and V8's ray unchanged.
+ *
+ * Inputs (device f32), batched over B views, per view b: the frame depth_f
+ * [B][Hf][Wf] with intrinsics Kf [B][4] = fx, fy, cx, cy; the current estimate
+ * pose [B][3][4] world->camera (Rra = pose[r][a], t_r = pose[r][3]); the model
+ * maps as V8 leaves them, depth_m [B][Hm][Wm] and normals_m [B][Hm][Wm][3] (world
+ * frame, unit or all-zero), with their camera pose_m [B][3][4] (M below) and Km
+ * [B][4] = fxm, fym, cxm, cym.  The two image sizes may differ (each below 2^20
+ * per side and 2^31 pixels, B <= 65535).  Gates: dist2 > 0, the squared distance
+ * limit; cos2 in [0, 1), the squared cosine limit, or any negative value to
+ * switch the normal gate off.
+ *
+ * View skip rule (V5's): a non-finite entry or one of magnitude >= 2^60 in pose,
+ * pose_m, Kf or Km, or fx, fy, fxm or fym of 0, gives zero sums for the view.
+ *
+ * Frame pixel (v,u), pixel centres at integer coordinates, d = depth_f[b][v][u]:
+ * 1 Back-projection.  Reject unless d > 0 and d < 2^60 (a NaN fails: "the depth
+ *   test").  pc = (((f32(u) - cx)/fx) d, ((f32(v) - cy)/fy) d, d);
+ *   q_r = pc_r - t_r;  pw_a = (R0a q0 + R1a q1) + R2a q2.
+ * 2 Association (V5's projection into the model camera).
+ *   c_r = ((M_r0 pw_x + M_r1 pw_y) + M_r2 pw_z) + M_r3; reject unless
+ *   2^-60 <= c_Z < 2^60; iz = 1/c_Z; um = floor((fxm c_X) iz + (cxm + 0.5)),
+ *   vm = floor((fym c_Y) iz + (cym + 0.5)); reject unless 0 <= um < Wm and
+ *   0 <= vm < Hm (a NaN fails).  dm = depth_m[b][vm][um]: reject unless dm > 0.
+ *   nm = normals_m[b][vm][um]: reject when all three are 0 or one is not finite.
+ * 3 Model vertex, by V8's ray of pixel (vm,um), so that a V8 depth gives back
+ *   V8's hit point: dcx = (f32(um) - cxm)/fxm; dcy = (f32(vm) - cym)/fym;
+ *   o_a = -((M0a M03 + M1a M13) + M2a M23);  dw_a = (M0a dcx + M1a dcy) + M2a;
+ *   vmod_a = o_a + dm dw_a.
+ * 4 Distance gate.  e_a = pw_a - vmod_a; accept iff
+ *   (e_x e_x + e_y e_y) + e_z e_z <= dist2.
+ * 5 Normal gate, only when cos2 >= 0 (no square root, no division: the mask is
+ *   bit-exact).  The neighbours (v,u+1) and (v+1,u) must lie in the image and pass
+ *   the depth test, else reject.  With pc' of the right and pc" of the lower
+ *   neighbour (step 1's formula): a = pc' - pc, bv = pc" - pc,
+ *   c = bv x a = (bv_y a_z - bv_z a_y, bv_z a_x - bv_x a_z, bv_x a_y - bv_y a_x)
+ *   (two products and one subtraction each; it points towards the camera),
+ *   cw_a = (R0a c0 + R1a c1) + R2a c2,  dotv = (cw_x nm_x + cw_y nm_y) + cw_z nm_z,
+ *   cc = (cw_x cw_x + cw_y cw_y) + cw_z cw_z; accept iff dotv > 0 and
+ *   dotv dotv >= cos2 cc.
+ * 6 Row.  r = (nm_x e_x + nm_y e_y) + nm_z e_z;  J = (pw x nm, nm), six f32, the
+ *   cross product written as in step 5.
+ *
+ * Sums (f64) over the accepted pixels of a view, 29 doubles, sums [B][29]:
+ *   [0..20] A_ij = sum f64(J_i) f64(J_j), i <= j, upper triangle row-major;
+ *   [21..26] g_i = sum f64(J_i) f64(r);  [27] E = sum f64(r)^2;  [28] n, the count.
+ * Every product of two f32 is exact in f64, so only the order of the additions is
+ * implementation-defined; it is a fixed function of the shapes (no floating-point
+ * atomics, nothing depends on the CU count or the dispatch order): two runs give
+ * the same bits on any device.  The order: 16 x 16 pixel tiles in row-major order,
+ * nt of them; a workgroup takes share = max(4, ceil(nt/1024)) consecutive tiles; a
+ * pixel's lane is 8 (v mod 8) + (u mod 8) of wave 2 ((v mod 16) div 8) +
+ * ((u mod 16) div 8); a lane adds its pixels in tile order, the 64 lanes of a
+ * wave are added by the binary tree x_l += x_(l + off), off = 32, 16, .. 1, the 4
+ * waves in order, and the P workgroups' partials in 32 runs of ceil(P/32)
+ * consecutive ones, each run in order, then the runs in order.
+ * mask (nullable) [B][Hf][Wf] u8: 1 where the pixel was accepted, else 0.
+ *
+ * Solve and update (f64, per view), delta = (omega, v) with A delta = -g by LDL^T
+ * without pivoting (d_j = A_jj - sum_(m<j) (L_jm L_jm) d_m).  The view is LOST when
+ * n < min_pairs or a pivot is not above 1e-12 trace(A): its pose stays as it is,
+ * bit for bit, and its later iterations are no-ops (their log records carry zero
+ * sums and delta and the status).  A view taken out by the skip rule has zero
+ * sums, is lost too, and carries status 2.  Otherwise dR = Rodrigues(omega)
+ * (theta = |omega|, k = omega/theta, dR = cos(theta) I + (1 - cos(theta)) k k^T +
+ * sin(theta) [k]x; I when theta = 0), R' = R dR^T, t' = t - R' v: the world-frame
+ * increment pw <- dR pw + v applied to the world->camera pose.  The pose is
+ * carried in f64 across the iterations of one call; each iteration's per-pixel
+ * arithmetic reads its f32 rounding.
+ *
+ * sfmhip_icp_normal_equations: one linearisation at the given poses.
+ * sfmhip_icp_track: n_iters iterations (2 n_iters plain kernel launches on the
+ * stream, no host round trip); pose_inout [B][3][4] f32 device; log (nullable,
+ * device) [B][n_iters][36] f64: the 29 sums, the 6 delta, the status (0 ok,
+ * 1 lost, 2 skipped view).
+ * B, Hf Wf or n_iters of 0: a no-op.  dist2 <= 0, cos2 >= 1 (or either NaN),
+ * min_pairs < 6: SFMHIP_E_ARG.  An empty model image (Hm Wm = 0, the model maps
+ * may be null) with a non-empty frame is valid and gives lost views.  Both calls
+ * are asynchronous on the stream; scratch comes from the library pool.           */
+int sfmhip_icp_normal_equations(const float* depth_f, const float* Kf, const float* pose, int B, int Hf, int Wf,
+                                const float* depth_m, const float* normals_m, const float* pose_m,
+                                const float* Km, int Hm, int Wm, float dist2, float cos2,
+                                double* sums, uint8_t* mask /* nullable */, void* stream);
+int sfmhip_icp_track(const float* depth_f, const float* Kf, int B, int Hf, int Wf,
+                     const float* depth_m, const float* normals_m, const float* pose_m,
+                     const float* Km, int Hm, int Wm, float dist2, float cos2,
+                     int n_iters, int min_pairs, float* pose_inout, double* log /* nullable */,
+                     void* stream);
+
 /* ---- §8f row 2: geometric verification (batched over image pairs) --------
  * cv2.findEssentialMat(pts0, pts1, K, method=cv2.RANSAC, prob=0.999,
  * threshold=1) at matching.py:134 and sfm.py:108 (OpenCV five-point.cpp +
