@@ -20,7 +20,8 @@ from .geometry import (Rodrigues, ba_sparse, calculate_reprojection_error,  # no
 from .voxel import (MASK_PLENOXEL, MASK_SDF, VoxelGrid, icp_normal_equations, icp_track, tsdf_block_table,  # noqa: F401,E501
                     tsdf_cull_stats, tsdf_integrate, tsdf_extract_surface, tsdf_integrate_colour, tsdf_layer_cost,
                     tsdf_layer_stats, tsdf_raycast, tsdf_track, voxel_traversal)
-from . import bow, mesh, pipeline, reconstruct, tracks, verify  # noqa: F401,E402
+from .mvs import census_transform, depth_consistency, inverse_depth_planes, mvs_depth, plane_sweep  # noqa: F401
+from . import bow, mesh, mvs, pipeline, reconstruct, tracks, verify  # noqa: F401,E402
 from .mesh import write_ply  # noqa: F401
 from .bow import kmeans  # noqa: F401
 from .reconstruct import triangulate  # noqa: F401

@@ -103,6 +103,10 @@ SIGNATURES = {
                             _p, _p, _p, _p, _p],
     "sfmhip_icp_normal_equations": [_p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _i32, _i32, _f32, _f32, _p, _p, _p],
     "sfmhip_icp_track": [_p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _i32, _i32, _f32, _f32, _i32, _i32, _p, _p, _p],
+    "sfmhip_census": [_p, _i32, _i32, _i32, _p, _p],
+    "sfmhip_plane_sweep": [_p, _p, _p, _i32, _i32, _i32, _p, _p, _i32, _i32, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p,
+                           _p, _p, _p],
+    "sfmhip_depth_consistency": [_p, _p, _p, _i32, _i32, _i32, _p, _p, _i32, _i32, _f32, _i32, _p, _p, _p],
     "sfmhip_find_essential": [_p, _p, _p, _i32, _p, _f64, _f64, _i32, _p, _p, _p, _p, _p, _p, _p],
     "sfmhip_recover_pose": [_p, _i64, _p, _p, _p, _i32, _p, _p, _f64, _p, _p, _p, _p, _p],
     "sfmhip_pnp_ransac": [_p, _p, _p, _i32, _p, _i32, _f64, _f64, _p, _p, _p, _p, _p, _p, _p, _p],

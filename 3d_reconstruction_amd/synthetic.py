@@ -251,3 +251,74 @@ def tsdf_scene_colour(depth, poses, K):
         out[f, ..., :3] = torch.where((d > 0)[..., None], rgb, torch.zeros_like(rgb))
         out[f, ..., 3] = 255
     return out
+
+
+# ---------------------------------------------------------------------------
+def _value_noise(X, cell):
+    """Trilinear value noise over the integer lattice q = floor(X / cell); lattice values
+    0..255 from an int64 hash that wraps as numpy's int64 does."""
+    g = X / cell
+    q = torch.floor(g)
+    f = g - q
+    q = q.to(torch.int64)
+    out = torch.zeros_like(g[..., 0])
+    for dz in (0, 1):
+        for dy in (0, 1):
+            for dx in (0, 1):
+                h = ((q[..., 0] + dx) * 73856093) ^ ((q[..., 1] + dy) * 19349663) ^ ((q[..., 2] + dz) * 83492791)
+                h = (h ^ (h >> 13)) * 1274126177
+                val = ((h ^ (h >> 16)) & 255).to(g.dtype)
+                w = (f[..., 0] if dx else 1 - f[..., 0]) * (f[..., 1] if dy else 1 - f[..., 1]) * \
+                    (f[..., 2] if dz else 1 - f[..., 2])
+                out = out + w * val
+    return out
+
+
+def mvs_scene(Hd=192, Wd=256, focal=220.0, cx=128.0, cy=96.0, n_views=5, device="cpu"):
+    """Posed grey images of :func:`tsdf_scene`'s floor and spheres for multi-view stereo: camera
+    i at (3 cos a, 2.2, 3 sin a), a = 90 + 5 (i - 2) degrees, looking at the origin.  The depth
+    is analytic in f64 (the ray maths of :func:`tsdf_scene`) and rounded to f32; the grey value
+    of a pixel is clip(rint(0.6 N(X, 0.08) + 0.4 N(X + 17.3, 0.036)), 0, 255) at its world hit
+    point X (f64 back-projection as in :func:`tsdf_scene_colour`), N trilinear value noise, so
+    the views agree on the texture of a surface point; 0 where a ray hits nothing.
+    Returns grey (V,Hd,Wd) u8, depth (V,Hd,Wd) f32, poses (V,3,4) f32, K (V,4) f32."""
+    f64 = torch.float64
+    us = torch.arange(Wd, device=device, dtype=f64)[None, :]
+    vs = torch.arange(Hd, device=device, dtype=f64)[:, None]
+    poses = np.empty((n_views, 3, 4), np.float32)
+    K = np.tile(np.array([[focal, focal, cx, cy]], np.float32), (n_views, 1))
+    depth = torch.empty((n_views, Hd, Wd), dtype=torch.float32, device=device)
+    grey = torch.zeros((n_views, Hd, Wd), dtype=torch.uint8, device=device)
+    for i in range(n_views):
+        a = math.radians(90.0 + 5.0 * (i - 2))
+        c_np = np.array([3.0 * math.cos(a), 2.2, 3.0 * math.sin(a)])
+        R_np, t_np = _look_at(c_np)
+        poses[i, :, :3], poses[i, :, 3] = R_np, t_np
+        R = torch.tensor(R_np, dtype=f64, device=device)
+        c = torch.tensor(c_np, dtype=f64, device=device)
+        dc = torch.stack(torch.broadcast_tensors((us - cx) / focal, (vs - cy) / focal,
+                                                 torch.ones(1, device=device, dtype=f64)), -1)
+        dw = dc @ R
+        best = torch.full(dw.shape[:2], float("inf"), device=device, dtype=f64)
+        for (sx, sy, sz, sr) in SPHERES:
+            oc = c - torch.tensor([sx, sy, sz], device=device, dtype=f64)
+            qa = (dw * dw).sum(-1)
+            qb = 2 * (dw * oc).sum(-1)
+            qc = float((oc * oc).sum() - sr * sr)
+            disc = qb * qb - 4 * qa * qc
+            tt = (-qb - torch.sqrt(disc.clamp_min(0))) / (2 * qa)
+            ok = (disc >= 0) & (tt > 0)
+            best = torch.where(ok & (tt < best), tt, best)
+        tp = (FLOOR_Y - c[1]) / dw[..., 1]
+        okp = (tp > 0) & (dw[..., 1].abs() > 1e-9)
+        best = torch.where(okp & (tp < best), tp, best)
+        depth[i] = torch.where(torch.isfinite(best), best, torch.zeros_like(best)).to(torch.float32)
+        # texture at the hit point of the rounded depth, through the rounded pose
+        d = depth[i].to(f64)
+        P = torch.tensor(poses[i], dtype=f64, device=device)
+        fx, fy, cxx, cyy = (float(x) for x in K[i])
+        pc = torch.stack(torch.broadcast_tensors((us - cxx) / fx * d, (vs - cyy) / fy * d, d), -1)
+        X = (pc - P[:, 3]) @ P[:, :3]
+        g = torch.clamp(torch.round(0.6 * _value_noise(X, 0.08) + 0.4 * _value_noise(X + 17.3, 0.036)), 0, 255)
+        grey[i] = torch.where(d > 0, g, torch.zeros_like(g)).to(torch.uint8)
+    return grey, depth, torch.from_numpy(poses).to(device), torch.from_numpy(K).to(device)

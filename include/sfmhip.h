@@ -656,6 +656,82 @@ int sfmhip_icp_track(const float* depth_f, const float* Kf, int B, int Hf, int W
                      int n_iters, int min_pairs, float* pose_inout, double* log /* nullable */,
                      void* stream);
 
+/* ---- V10: dense depth from posed images, census plane-sweep stereo (build-defined)
+ * Multi-view stereo: V posed grey images in, one depth map per reference view out,
+ * in the conventions of V5 (0 = invalid), so the maps feed sfmhip_tsdf_integrate as
+ * they are.  The reference has no counterpart.  Restated in numpy by
+ * tests/mvs_ref.py.  The costs are integers; every f32 operation is one IEEE
+ * round-to-nearest step in the order written, no FMA: every output is defined to
+ * the bit.
+ *
+ * Views: one size (H, W) for all; img [V][H][W] u8; poses [V][3][4] f32
+ * world->camera; K [V][4] = fx, fy, cx, cy; pixel centres at integer coordinates.
+ * View skip rule (V5's): a non-finite entry or one of magnitude >= 2^60 in a
+ * view's pose or intrinsics, or fx or fy of 0, makes the view invalid.  An invalid
+ * reference (or a refs entry outside [0, V)) gives all-zero outputs; an invalid
+ * source, a srcs entry of -1 ("none") or one outside [0, V) is out of view
+ * everywhere.
+ *
+ * 1 Census (sfmhip_census), cen [V][H][W] u64, 7 x 7: for (dy, dx) from (-3, -3) to
+ *   (3, 3) in row-major order without the centre, bit i (i = 0..47 in that order)
+ *   is 1 iff the neighbour lies inside the image and img[nb] > img[centre]; bits
+ *   48..63 are 0.
+ * 2 Relative pose per (reference r, source s), in f64 from the f32 entries:
+ *   Rrel[i][j] = (Rs[i][0] Rr[j][0] + Rs[i][1] Rr[j][1]) + Rs[i][2] Rr[j][2];
+ *   trel[i] = ts[i] - ((Rrel[i][0] tr[0] + Rrel[i][1] tr[1]) + Rrel[i][2] tr[2]) with
+ *   the f64 Rrel; both then rounded to f32 (R, t below).
+ * 3 Raw cost of reference pixel (v, u), plane depth z = planes[k], source s (f32):
+ *   dx = (f32(u) - cx)/fx; dy = (f32(v) - cy)/fy (V8's ray); X = dx z; Y = dy z;
+ *   xc = ((R00 X + R01 Y) + R02 z) + t0, yc and zc by rows 1 and 2; visible requires
+ *   2^-60 <= zc < 2^60; iz = 1/zc; pu = floor((fx_s xc) iz + (cx_s + 0.5)),
+ *   pv = floor((fy_s yc) iz + (cy_s + 0.5)) (V5's rule); visible also requires
+ *   0 <= pu < W and 0 <= pv < H (a NaN fails).  Visible: c = popcount(cen[r][v][u] ^
+ *   cen[s][pv][pu]); not visible: c = penalty.  raw[k][v][u] = sum_s c over all S
+ *   entries of the reference's source list; nv[k][v][u] = the number of visible ones.
+ * 4 Aggregation: ag[k][v][u] = the sum of raw[k] over the (2a+1)^2 window around
+ *   (v, u); a window position outside the image contributes penalty S.  int32.
+ * 5 Winner: k* = the smallest k attaining min_k ag; best = ag[k*]; second = the
+ *   minimum of ag[k] over |k - k*| >= 2, or INT32_MAX if there is none.
+ * 6 Sub-plane depth: inv[k] = 1/planes[k] (an f32 division); c0, cm, cp = ag at k*,
+ *   k* - 1, k* + 1 as f32; den = (cm - c0) + (cp - c0); off = (cm - cp)/(2 den) if
+ *   0 < k* < P - 1 and den > 0, else 0; step = inv[k*+1] - inv[k*] if off >= 0, else
+ *   inv[k*] - inv[k*-1]; depth = 1/(inv[k*] + off step).
+ * 7 Validity: depth = 0 unless 0 < k* < P - 1, nv[k*][v][u] >= min_views and
+ *   256 best <= uniq second (compared in int64; uniq in 0..256, 256 disables it).
+ * 8 Consistency (sfmhip_depth_consistency): for reference r with d_r = depth[r] and
+ *   each source s of its list, from the same array depth [V][H][W]: a pixel with
+ *   d_r > 0 is reprojected exactly as in step 3 with z = d_r; the source is
+ *   consistent iff the pixel is visible, ds = depth[s][pv][pu] > 0 and
+ *   fabsf(ds - zc) <= eps zc.  count [R][H][W] u8 = the number of consistent
+ *   sources (0 where d_r is not > 0); filtered [R][H][W] = d_r where d_r > 0 and
+ *   count >= min_consistent, else 0.  depth and filtered must not overlap.
+ *
+ * Limits: 1 <= S <= 16, 0 <= a = agg_radius <= 3, 0 <= penalty <= 48, 1 <= P <= 65535,
+ * 0 <= uniq <= 256, min_views >= 0, eps finite and >= 0, min_consistent >= 0,
+ * R <= 65535, H and W below 2^20 and H W below 2^31: otherwise SFMHIP_E_ARG, like a
+ * null pointer, without touching the GPU.  ag <= 48 49 16 < 2^16, so (ag << 16) | k
+ * is a u32 key whose minimum is the winner with the tie rule built in.  P < 3 is
+ * legal and gives all-invalid maps.  planes [P] must be finite, positive and
+ * strictly monotonic in either direction: they are device memory, so this is the
+ * caller's duty (the Python wrapper checks it); the steps above are defined for any
+ * values.  R = 0 or H W = 0 (V = 0 or H W = 0 for the census) is a no-op without a
+ * launch.
+ *
+ * All arrays are device memory: refs [R] i32, srcs [R][S] i32, planes [P] f32;
+ * outputs depth [R][H][W] f32 and the nullable diagnostics kstar [R][H][W] i32,
+ * best, second (i32) and nv (u8) = nv[k*].  The calls are asynchronous plain
+ * launches on the stream; scratch comes from the library pool.  No atomics: two
+ * runs give the same bits.                                                      */
+int sfmhip_census(const uint8_t* img, int V, int H, int W, uint64_t* cen, void* stream);
+int sfmhip_plane_sweep(const uint64_t* cen, const float* poses, const float* K, int V, int H, int W,
+                       const int32_t* refs, const int32_t* srcs, int R, int S,
+                       const float* planes, int P, int agg_radius, int penalty, int uniq, int min_views,
+                       float* depth, int32_t* kstar /* nullable */, int32_t* best /* nullable */,
+                       int32_t* second /* nullable */, uint8_t* nv /* nullable */, void* stream);
+int sfmhip_depth_consistency(const float* depth, const float* poses, const float* K, int V, int H, int W,
+                             const int32_t* refs, const int32_t* srcs, int R, int S, float eps,
+                             int min_consistent, uint8_t* count, float* filtered, void* stream);
+
 /* ---- §8f row 2: geometric verification (batched over image pairs) --------
  * cv2.findEssentialMat(pts0, pts1, K, method=cv2.RANSAC, prob=0.999,
  * threshold=1) at matching.py:134 and sfm.py:108 (OpenCV five-point.cpp +
