@@ -107,6 +107,10 @@ SIGNATURES = {
     "sfmhip_plane_sweep": [_p, _p, _p, _i32, _i32, _i32, _p, _p, _i32, _i32, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p,
                            _p, _p, _p],
     "sfmhip_depth_consistency": [_p, _p, _p, _i32, _i32, _i32, _p, _p, _i32, _i32, _f32, _i32, _p, _p, _p],
+    "sfmhip_cost_volume": [_p, _p, _p, _i32, _i32, _i32, _p, _p, _i32, _i32, _p, _i32, _i32, _i32, _p, _p],
+    "sfmhip_sgm_aggregate": [_p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p],
+    "sfmhip_volume_select": [_p, _p, _p, _i32, _i32, _i32, _p, _p, _i32, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p,
+                             _p],
     "sfmhip_find_essential": [_p, _p, _p, _i32, _p, _f64, _f64, _i32, _p, _p, _p, _p, _p, _p, _p],
     "sfmhip_recover_pose": [_p, _i64, _p, _p, _p, _i32, _p, _p, _f64, _p, _p, _p, _p, _p],
     "sfmhip_pnp_ransac": [_p, _p, _p, _i32, _p, _i32, _f64, _f64, _p, _p, _p, _p, _p, _p, _p, _p],

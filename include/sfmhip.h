@@ -721,7 +721,43 @@ int sfmhip_icp_track(const float* depth_f, const float* Kf, int B, int Hf, int W
  * outputs depth [R][H][W] f32 and the nullable diagnostics kstar [R][H][W] i32,
  * best, second (i32) and nv (u8) = nv[k*].  The calls are asynchronous plain
  * launches on the stream; scratch comes from the library pool.  No atomics: two
- * runs give the same bits.                                                      */
+ * runs give the same bits.
+ *
+ * Semi-global smoothing (optional; sfmhip_cost_volume, sfmhip_sgm_aggregate,
+ * sfmhip_volume_select; restated by tests/mvs_sgm_ref.py).  Between steps 4 and 5:
+ * 4a Cost volume: vol[r][v][u][k] = ag[k][v][u] of step 4 as u16 (ag <= 37632), the
+ *   plane index innermost.  An invalid reference gives an all-zero slice.
+ * 4b Path aggregation with integers 0 <= p1 <= p2 <= 16383 and a non-zero 8-bit
+ *   path_mask whose bit i selects the direction d_i = (dv, du) of (0,+1), (0,-1),
+ *   (+1,0), (-1,0), (+1,+1), (+1,-1), (-1,+1), (-1,-1).  For a selected d, pixel
+ *   p = (v, u) and predecessor q = p - d: L_d(p, k) = vol(p, k) if q lies outside
+ *   the image; otherwise, with m = min_j L_d(q, j),
+ *   L_d(p, k) = vol(p, k) + min(L_d(q, k), L_d(q, k-1) + p1 [only if k > 0],
+ *   L_d(q, k+1) + p1 [only if k < P-1], m + p2) - m.  So vol <= L_d <= vol + p2 < 2^16.
+ *   sm[r][v][u][k] = the sum of L_d(p, k) over the selected d, u32, below 2^19.
+ * 5'-7' Selection: steps 5, 6 and 7 as written with sm in place of ag (the smallest
+ *   k of the minimum; second over |k - k*| >= 2 or INT32_MAX; the same f32 parabola;
+ *   256 best <= uniq second in int64).  nv stays step 3's count at planes[k*]; it
+ *   does not depend on the smoothing.  An invalid reference gives all-zero outputs.
+ * Limits of this mode: 1 <= P <= 256 for sfmhip_sgm_aggregate and
+ * sfmhip_volume_select; p1 > p2, p2 > 16383 or path_mask outside [1, 255] is
+ * SFMHIP_E_ARG, like a null pointer and the limits above, without touching the
+ * GPU; R = 0 or H W = 0 is a no-op without a launch.  sfmhip_sgm_aggregate takes no
+ * cameras and is defined for any u16 volume; sfmhip_volume_select is defined for
+ * sm entries below 2^24.  sm must not overlap vol.  Plain asynchronous launches on
+ * the stream (one per selected direction: the first writes sm, the others add to
+ * it, no atomics); two runs give the same bits.                                  */
+int sfmhip_cost_volume(const uint64_t* cen, const float* poses, const float* K, int V, int H, int W,
+                       const int32_t* refs, const int32_t* srcs, int R, int S,
+                       const float* planes, int P, int agg_radius, int penalty,
+                       uint16_t* vol /* [R][H][W][P] */, void* stream);
+int sfmhip_sgm_aggregate(const uint16_t* vol, int R, int H, int W, int P, int p1, int p2, int path_mask,
+                         uint32_t* sm /* [R][H][W][P] */, void* stream);
+int sfmhip_volume_select(const uint32_t* sm, const float* poses, const float* K, int V, int H, int W,
+                         const int32_t* refs, const int32_t* srcs, int R, int S,
+                         const float* planes, int P, int uniq, int min_views,
+                         float* depth, int32_t* kstar /* nullable */, int32_t* best /* nullable */,
+                         int32_t* second /* nullable */, uint8_t* nv /* nullable */, void* stream);
 int sfmhip_census(const uint8_t* img, int V, int H, int W, uint64_t* cen, void* stream);
 int sfmhip_plane_sweep(const uint64_t* cen, const float* poses, const float* K, int V, int H, int W,
                        const int32_t* refs, const int32_t* srcs, int R, int S,
