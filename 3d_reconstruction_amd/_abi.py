@@ -67,6 +67,11 @@ SIGNATURES = {
                                  _p, _p, _p, _p, _p],
     "sfmhip_match_pairs_exact_i16": [_p, _p, _p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _i32, _i32,
                                      _i32, _p, _p, _p],
+    "sfmhip_desc_quantize_fp6": [_p, _i32, _i32, _i32, _p, _p, _p, _p],
+    "sfmhip_match_pairs_exact_fp6": [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _i32, _i32, _i32, _p, _p,
+                                     _p],
+    "sfmhip_match_pairs_exact_fp6_i16": [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _i32, _i32, _i32, _p,
+                                         _p, _p],
     "sfmhip_vq": [_p, _i64, _p, _i32, _i32, _p, _p, _p],
     "sfmhip_word_histogram": [_p, _p, _i32, _i32, _p, _p],
     "sfmhip_kmeans_update": [_p, _i64, _i32, _p, _i32, _p, _p, _p],

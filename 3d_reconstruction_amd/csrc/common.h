@@ -59,6 +59,7 @@ void scratch_free(void* p, hipStream_t s);
 struct Knobs {
     int tsdf_latency;   // SFMHIP_TSDF_LATENCY: -1 auto, 0 whole-grid mode, 1 latency mode
     int match_cert;     // SFMHIP_MATCH_CERT: 0 sends every row of the exact float mode to the f64 pass
+    int match_fp6;      // SFMHIP_MATCH_FP6: 0 runs the sfmhip_match_pairs_exact_fp6 entries on the int8 value-only kernel
     int ess_mono;       // SFMHIP_ESS_MONO: 1 runs the one-workgroup-per-pair essential RANSAC kernel
     int ess_rece;       // SFMHIP_ESS_RECE: essential models whose E is kept per record (0: all re-solved)
     int dlt_qr;         // SFMHIP_DLT_QR: 1 runs the QR DLT for every observation (no normal-equation pass)

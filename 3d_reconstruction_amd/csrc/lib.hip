@@ -158,6 +158,7 @@ static Knobs read_knobs() {
     Knobs k;
     k.tsdf_latency = env_knob("SFMHIP_TSDF_LATENCY", -1);
     k.match_cert = env_knob("SFMHIP_MATCH_CERT", 1);
+    k.match_fp6 = env_knob("SFMHIP_MATCH_FP6", 1);
     k.ess_mono = env_knob("SFMHIP_ESS_MONO", 0);
     k.ess_rece = env_knob("SFMHIP_ESS_RECE", 1 << 20);
     k.dlt_qr = env_knob("SFMHIP_DLT_QR", 0);

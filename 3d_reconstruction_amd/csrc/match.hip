@@ -112,10 +112,77 @@ __global__ void prepare_kernel(const int8_t* __restrict__ desc, int n_rows, int 
     keys[row] = (r < nk[img]) ? (-s * 128 + low) : (INT_MIN + low);
 }
 
-// h = keys >> 8 (match_kernel's value-only form), one call's scratch.
-__global__ void key_values_kernel(const int32_t* __restrict__ keys, int64_t n, int32_t* __restrict__ h) {
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x)
-        h[e] = keys[e] >> 8;
+// h = keys >> 8 (match_kernel's value-only form), one call's scratch; hf (nullable) = the same values in
+// f32 for match_fp6_kernel's accumulator chains (|h| <= 2^23: the conversion is exact).
+__global__ void key_values_kernel(const int32_t* __restrict__ keys, int64_t n, int32_t* __restrict__ h,
+                                  float* __restrict__ hf) {
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+        const int v = keys[e] >> 8;
+        h[e] = v;
+        if (hf) hf[e] = (float)v;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// FP6 (e2m3) integer grid (DESIGN.md K1''): f32 -> g, the point of
+//   G = {0..15 step 1, 16..30 step 2, 32..60 step 4} (both signs)
+// nearest to y = 127 x (one f32 product), |y| clipped at 60, and its 6-bit code
+//   code = sign << 5 | n,   n = exponent << 3 | mantissa (bias 1),   value(code) = +-g / 8:
+//   n = g (g < 16), 8 + g / 2 (16 <= g < 32), 16 + g / 4 (g >= 32).
+// Tie rule: nearest, ties to the even code n (at every midpoint of G the two neighbours' n differ by
+// one; within a step rintf's ties-to-even on |y| / step is that rule, and the region ends 16 and 32 have
+// even n).  g = 0 has code 0 whatever the sign of y.  Padded rows: g = 0, code 0.
+// One thread per 32 elements: g as int8 [..][d], codes as one 32-byte chunk per 32 elements, code e at
+// bits 6 e .. 6 e + 5 of the chunk's first 24 bytes (little endian), the last 8 bytes zero — a row of d
+// elements is d bytes in both arrays.
+__device__ __forceinline__ int fp6_grid_index(float y, int* g) {
+    const float t = fminf(fabsf(y), 60.f);
+    int n, m;
+    if (t < 16.f) { m = (int)__builtin_rintf(t); n = m; }
+    else if (t < 32.f) { const int r = (int)__builtin_rintf(0.5f * t); m = 2 * r; n = r + 8; }
+    else { const int r = (int)__builtin_rintf(0.25f * t); m = 4 * r; n = r + 16; }
+    const bool neg = y < 0.f && m > 0;
+    *g = neg ? -m : m;
+    return n | (neg ? 32 : 0);
+}
+__global__ void quantize_fp6_kernel(const float* __restrict__ in, int64_t n_chunks, int d, int m_pad,
+                                    const int32_t* __restrict__ nk, int8_t* __restrict__ g,
+                                    uint8_t* __restrict__ code) {
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n_chunks;
+         c += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t e0 = c * 32, row = e0 / d;
+        const int img = (int)(row / m_pad), r = (int)(row % m_pad);
+        const bool valid = r < nk[img];
+        unsigned gw[8], cw[8];
+#pragma unroll
+        for (int w = 0; w < 8; ++w) gw[w] = cw[w] = 0u;
+        if (valid) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const float4 x = *reinterpret_cast<const float4*>(in + e0 + 4 * q);
+                const float v[4] = {x.x, x.y, x.z, x.w};
+                unsigned pk = 0u;   // 4 codes = 24 bits = bytes 3 q .. 3 q + 2 of the chunk
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    int gv;
+                    const int cd = fp6_grid_index(127.f * v[t], &gv);
+                    gw[q] |= (unsigned)(gv & 0xff) << (8 * t);
+                    pk |= (unsigned)cd << (6 * t);
+                }
+#pragma unroll
+                for (int t = 0; t < 3; ++t) {
+                    const int byte = 3 * q + t;
+                    cw[byte >> 2] |= ((pk >> (8 * t)) & 0xffu) << (8 * (byte & 3));
+                }
+            }
+        }
+        uint4* go = reinterpret_cast<uint4*>(g + e0);
+        uint4* co = reinterpret_cast<uint4*>(code + e0);
+        go[0] = make_uint4(gw[0], gw[1], gw[2], gw[3]);
+        go[1] = make_uint4(gw[4], gw[5], gw[6], gw[7]);
+        co[0] = make_uint4(cw[0], cw[1], cw[2], cw[3]);
+        co[1] = make_uint4(cw[4], cw[5], cw[6], cw[7]);
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -248,6 +315,108 @@ __device__ __forceinline__ int certify(int d1lo, int d1hi, int d2lo, int d2hi, d
     if (rd2 * lo1 >= rn2 * hi2) return 0;
     if (hi1 < lo2 && rd2 * hi1 < rn2 * lo2) return 1;
     return -1;
+}
+
+// The value-only form's tail, shared by match_kernel<.., VG> and match_fp6_kernel: from a lane's top two
+// group maxima w1 >= w2 and the range wr where w1 rose (per query tile s) to the row's graph entry: the
+// lane-group merge, the pre-test, the rescan of the recorded group for surviving rows and the final
+// certificate (match_kernel's comment).  `desc` holds the int8 rows the rescan dots (the kernel's own
+// operands, or the grid values g of the FP6 form), bkeys the values h_j of image b.
+template <int D, int MF, int NS, int VG, typename OutT>
+__device__ __forceinline__ void value_only_tail(const int (&w1)[NS], const int (&w2)[NS], const int (&wr)[NS],
+                                                const int8_t* __restrict__ desc, const int8_t* __restrict__ bdesc,
+                                                const int32_t* __restrict__ bkeys, const int32_t* __restrict__ norms,
+                                                int a, int b, int m_pad, int na_rows, int ibase, int grp, int lr,
+                                                int lane, long long rn2, long long rd2, OutT* __restrict__ out_m,
+                                                const CertArgs& ca) {
+    constexpr int NG = 64 / MF;
+    // lanes of the NG groups hold the same query row, disjoint candidate rows: a value-only
+    // merge that carries the (range, lane group) of the larger best; lane group s keeps tile s
+    int v1 = INT_MIN, v2 = INT_MIN, loc = 0;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        int a1 = w1[s], a2 = w2[s], al = wr[s] * NG + grp;
+#pragma unroll
+        for (int off = MF; off < 64; off <<= 1) {
+            const int o1 = __shfl_xor(a1, off), o2 = __shfl_xor(a2, off), ol = __shfl_xor(al, off);
+            const bool mine = a1 > o1 || (a1 == o1 && al < ol);
+            a2 = max3i(min(a1, o1), a2, o2);
+            al = mine ? al : ol;
+            a1 = max(a1, o1);
+        }
+        if (s == grp) { v1 = a1; v2 = a2; loc = al; }
+    }
+    // v1 is the exact best; v2 (the second of the group maxima) is the largest value outside
+    // the group `loc`, a lower bound of the true second
+    const int i = ibase + grp * MF + lr;
+    int res = -1, na = 0, du1 = 0, hidx = -1;
+    double E = 0.0;
+    bool survivor = false;
+    if (i < na_rows) {   // na_rows <= m_pad
+        na = norms[(size_t)a * m_pad + i];
+        du1 = na - 2 * v1;                  // D1 in [du1 - 1, du1]
+        const int du2ub = na - 2 * v2;      // D2 in [du1 - 1, du2ub]
+        E = ca.erow[(size_t)a * m_pad + i] + ca.eimg[b];
+        // pre-test: a reject reads lo(D1) and hi(D2) only, and hi() of an upper bound of D2 is
+        // valid, so 0 is final; everything else goes on.  A forced row is marked from du2ub, or
+        // from the largest int8 distance where v2 is a padded row's value (all valid candidates
+        // in one group: the int16 mark holds sqrt(D2) only up to D 255^2)
+        if (ca.force)
+            res = undecided_mark<OutT>(min(du2ub, D * 255 * 255));
+        else
+            survivor = certify(max(du1 - 1, 0), du1, max(du1 - 1, 0), du2ub, E, ca.inv_s, (double)rn2,
+                               (double)rd2) != 0;
+    }
+    // the hidden second and the winner's index, surviving rows only, one row at a time by the
+    // whole wave: LPC lanes per candidate of the recorded group, each a D / LPC byte slice of
+    // <b_j, a_i>
+    constexpr int NC = 4 * VG;
+    constexpr int LPC = (64 / NC) < (D / 16) ? (64 / NC) : (D / 16);
+    constexpr int BPL = D / LPC;
+    const int c = min(lane / LPC, NC - 1), part = lane % LPC;
+    unsigned long long bal = __ballot(survivor);
+    while (bal) {
+        const int l = __builtin_ctzll(bal);
+        bal &= bal - 1;
+        const int ri = __shfl(i, l), rv = __shfl(v1, l), rl = __shfl(loc, l);
+        const int j0 = (rl / NG) * VG * MF + 4 * (rl % NG);   // candidate c: tile c / 4 of the range, row c % 4
+        const int j = j0 + (c >> 2) * MF + (c & 3);
+        const int8_t* pa = desc + ((size_t)a * m_pad + ri) * D + part * BPL;
+        const int8_t* pb = bdesc + (size_t)j * D + part * BPL;
+        int dot = 0;
+#pragma unroll
+        for (int w = 0; w < BPL / 16; ++w) {
+            const i32x4 x = *reinterpret_cast<const i32x4*>(pa + 16 * w);
+            const i32x4 y = *reinterpret_cast<const i32x4*>(pb + 16 * w);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) dot = __builtin_amdgcn_sdot4(x[e], y[e], dot, false);
+        }
+#pragma unroll
+        for (int off = 1; off < LPC; off <<= 1) dot += __shfl_xor(dot, off);
+        const int u = dot + bkeys[j];   // every lane of candidate c holds u_c
+        const bool hit = lane < NC * LPC && part == 0 && u == rv;
+        const unsigned long long hb = __ballot(hit);   // >= 1 candidate: the group's maximum is v1
+        // the largest value of the group's other candidates: v1 again when it occurs twice
+        int x = u == rv ? INT_MIN : u;
+#pragma unroll
+        for (int off = LPC; off < 64; off <<= 1) x = max(x, __shfl_xor(x, off));
+        if (lane == l) {
+            const bool one = __popcll(hb) == 1;
+            v2 = max(v2, one ? x : rv);
+            if (one) {
+                const int hc = __builtin_ctzll(hb) / LPC;
+                hidx = j0 + (hc >> 2) * MF + (hc & 3);
+            }
+        }
+    }
+    // the final decision on the exact second, as the per-distance top two gave it
+    if (survivor) {
+        const int du2 = na - 2 * v2;   // D2 in [du2 - 1, du2]
+        const int v = certify(max(du1 - 1, 0), du1, max(du2 - 1, 0), du2, E, ca.inv_s, (double)rn2, (double)rd2);
+        // an accepted row has v1 > v2, so exactly one candidate of its group attains v1
+        res = v == 0 ? -1 : (v > 0 && hidx >= 0) ? hidx : undecided_mark<OutT>(du2);
+    }
+    if (i < m_pad) out_m[i] = (OutT)res;
 }
 
 // One workgroup = one pair x (WAVES * NS * MF) query rows of image a.  Each
@@ -459,93 +628,8 @@ __global__ __launch_bounds__(64 * WAVES, 2) void match_kernel(
     }
 
     if constexpr (VO) {
-        // lanes of the NG groups hold the same query row, disjoint candidate rows: a value-only
-        // merge that carries the (range, lane group) of the larger best; lane group s keeps tile s
-        int v1 = INT_MIN, v2 = INT_MIN, loc = 0;
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            int a1 = w1[s], a2 = w2[s], al = wr[s] * NG + grp;
-#pragma unroll
-            for (int off = MF; off < 64; off <<= 1) {
-                const int o1 = __shfl_xor(a1, off), o2 = __shfl_xor(a2, off), ol = __shfl_xor(al, off);
-                const bool mine = a1 > o1 || (a1 == o1 && al < ol);
-                a2 = max3i(min(a1, o1), a2, o2);
-                al = mine ? al : ol;
-                a1 = max(a1, o1);
-            }
-            if (s == grp) { v1 = a1; v2 = a2; loc = al; }
-        }
-        // v1 is the exact best; v2 (the second of the group maxima) is the largest value outside
-        // the group `loc`, a lower bound of the true second
-        const int i = ibase + grp * MF + lr;
-        int res = -1, na = 0, du1 = 0, hidx = -1;
-        double E = 0.0;
-        bool survivor = false;
-        if (i < na_rows) {   // na_rows <= m_pad
-            na = norms[(size_t)a * m_pad + i];
-            du1 = na - 2 * v1;                  // D1 in [du1 - 1, du1]
-            const int du2ub = na - 2 * v2;      // D2 in [du1 - 1, du2ub]
-            E = ca.erow[(size_t)a * m_pad + i] + ca.eimg[b];
-            // pre-test: a reject reads lo(D1) and hi(D2) only, and hi() of an upper bound of D2 is
-            // valid, so 0 is final; everything else goes on.  A forced row is marked from du2ub, or
-            // from the largest int8 distance where v2 is a padded row's value (all valid candidates
-            // in one group: the int16 mark holds sqrt(D2) only up to D 255^2)
-            if (ca.force)
-                res = undecided_mark<OutT>(min(du2ub, D * 255 * 255));
-            else
-                survivor = certify(max(du1 - 1, 0), du1, max(du1 - 1, 0), du2ub, E, ca.inv_s, (double)rn2,
-                                   (double)rd2) != 0;
-        }
-        // the hidden second and the winner's index, surviving rows only, one row at a time by the
-        // whole wave: LPC lanes per candidate of the recorded group, each a D / LPC byte slice of
-        // <b_j, a_i>
-        constexpr int NC = 4 * VG;
-        constexpr int LPC = (64 / NC) < (D / 16) ? (64 / NC) : (D / 16);
-        constexpr int BPL = D / LPC;
-        const int c = min(lane / LPC, NC - 1), part = lane % LPC;
-        unsigned long long bal = __ballot(survivor);
-        while (bal) {
-            const int l = __builtin_ctzll(bal);
-            bal &= bal - 1;
-            const int ri = __shfl(i, l), rv = __shfl(v1, l), rl = __shfl(loc, l);
-            const int j0 = (rl / NG) * VG * MF + 4 * (rl % NG);   // candidate c: tile c / 4 of the range, row c % 4
-            const int j = j0 + (c >> 2) * MF + (c & 3);
-            const int8_t* pa = desc + ((size_t)a * m_pad + ri) * D + part * BPL;
-            const int8_t* pb = bdesc + (size_t)j * D + part * BPL;
-            int dot = 0;
-#pragma unroll
-            for (int w = 0; w < BPL / 16; ++w) {
-                const i32x4 x = *reinterpret_cast<const i32x4*>(pa + 16 * w);
-                const i32x4 y = *reinterpret_cast<const i32x4*>(pb + 16 * w);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) dot = __builtin_amdgcn_sdot4(x[e], y[e], dot, false);
-            }
-#pragma unroll
-            for (int off = 1; off < LPC; off <<= 1) dot += __shfl_xor(dot, off);
-            const int u = dot + bkeys[j];   // every lane of candidate c holds u_c
-            const bool hit = lane < NC * LPC && part == 0 && u == rv;
-            const unsigned long long hb = __ballot(hit);   // >= 1 candidate: the group's maximum is v1
-            // the largest value of the group's other candidates: v1 again when it occurs twice
-            int x = u == rv ? INT_MIN : u;
-#pragma unroll
-            for (int off = LPC; off < 64; off <<= 1) x = max(x, __shfl_xor(x, off));
-            if (lane == l) {
-                const bool one = __popcll(hb) == 1;
-                v2 = max(v2, one ? x : rv);
-                if (one) {
-                    const int hc = __builtin_ctzll(hb) / LPC;
-                    hidx = j0 + (hc >> 2) * MF + (hc & 3);
-                }
-            }
-        }
-        // the final decision on the exact second, as the per-distance top two gave it
-        if (survivor) {
-            const int du2 = na - 2 * v2;   // D2 in [du2 - 1, du2]
-            const int v = certify(max(du1 - 1, 0), du1, max(du2 - 1, 0), du2, E, ca.inv_s, (double)rn2, (double)rd2);
-            // an accepted row has v1 > v2, so exactly one candidate of its group attains v1
-            res = v == 0 ? -1 : (v > 0 && hidx >= 0) ? hidx : undecided_mark<OutT>(du2);
-        }
-        if (i < m_pad) out_m[i] = (OutT)res;
+        value_only_tail<D, MF, NS, VG, OutT>(w1, w2, wr, desc, bdesc, bkeys, norms, a, b, m_pad, na_rows, ibase, grp, lr,
+                                             lane, rn2, rd2, out_m, ca);
         return;
     }
     if constexpr (D <= 128) {
@@ -587,6 +671,143 @@ __global__ __launch_bounds__(64 * WAVES, 2) void match_kernel(
         if (dist1) dist1[(size_t)pair * m_pad + i] = d1;
         if (dist2) dist2[(size_t)pair * m_pad + i] = d2;
     }
+}
+
+// ---------------------------------------------------------------------------
+// match_fp6_kernel (DESIGN.md K1''): the value-only form of match_kernel<D, 16, 4, 4> with the filter's
+// dot products on v_mfma_scale_f32_16x16x128_f8f6f4 (twice the int8 rate per clock).  The operands are
+// the e2m3 codes of the grid values g (quantize_fp6_kernel; value g / 8) under the unit block scale 2^3
+// (E8M0 byte 130 in every byte of the scale register, so the op_sel byte does not matter): every
+// product is the integer g_a g_b.  |sum g_a g_b| <= D * 3600 <= 921,600 and h_j >= -2^23, so every
+// partial sum of  acc = <b_j, a_i> + h_j  is an integer below 2^24 in magnitude: exact in f32 whatever
+// the order the array sums in, and the identities of the value-only form (match_kernel's comment) hold
+// as they stand, with g in place of q.  The loop's maxima run in f32 (no conversion per distance); the
+// row's top two are converted to int once after the loop (exact) and value_only_tail takes over: its
+// rescan dots the int8 rows g.  Same workgroup shape, LDS ring, XCD remap and ranges as match_kernel;
+// a code row is D bytes (one 32-byte chunk per 32 codes), so Stager and swz_off carry over: a lane's
+// operand for k-step kk is the two 16-byte chunks 2 (4 kk + grp), + 1 of its row.
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+template <int D, typename OutT>
+__global__ __launch_bounds__(256, 2) void match_fp6_kernel(
+    const uint8_t* __restrict__ code, const int8_t* __restrict__ g, const int32_t* __restrict__ norms,
+    const int32_t* __restrict__ h, const float* __restrict__ hf, const int32_t* __restrict__ nk, int m_pad,
+    const int32_t* __restrict__ pairs, int n_iblk, int nwg, long long rn2, long long rd2,
+    OutT* __restrict__ m0, CertArgs ca) {
+    constexpr int MF = 16, NS = 4, WAVES = 4, VG = kValueOnlyTiles;
+    static_assert(D % 128 == 0, "one scaled MFMA takes 128 elements of k");
+    using S = Stager<D, WAVES>;
+    constexpr int KK = D / 128;                     // scaled MFMAs per output tile
+    constexpr int TILE = S::TILE;
+    constexpr int NT = 64 * WAVES;
+    constexpr int IW = MF * NS, IB = IW * WAVES;
+    constexpr int JT = kJB / MF;
+    constexpr int kScale = (int)0x82828282;         // E8M0 2^3 in every byte
+    constexpr float kLow = -16777216.f;             // below every value (padded rows: -2^23)
+
+    __shared__ __attribute__((aligned(16))) int8_t lds[2 * TILE + 2 * kJB * 4];
+
+    const int wg = xcd_remap(blockIdx.x, nwg);
+    const int pair = wg / n_iblk, ib = wg % n_iblk;
+    const int a = pairs[2 * pair], b = pairs[2 * pair + 1];
+    const int na_rows = nk[a], nb_rows = nk[b];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int grp = lane / MF, lr = lane % MF;
+    const int ibase = ib * IB + wave * IW;
+    OutT* out_m = m0 + (size_t)pair * m_pad;
+
+    if (ib * IB >= na_rows || nb_rows < 2) {  // block-uniform: nothing to match
+        const int iend = min(ib * IB + IB, m_pad);
+        for (int i = ib * IB + tid; i < iend; i += NT) out_m[i] = -1;
+        return;
+    }
+
+    const int8_t* bcode = reinterpret_cast<const int8_t*>(code) + (size_t)b * m_pad * D;
+    const int32_t* bhf = reinterpret_cast<const int32_t*>(hf) + (size_t)b * m_pad;   // f32 bits through the key DMA
+    const int nblk = (nb_rows + kJB - 1) / kJB;
+    int32_t* kbase = reinterpret_cast<int32_t*>(lds + 2 * TILE);
+
+    S::dma(bcode, bhf, lds, kbase, wave, lane);  // block 0 in flight
+
+    // Query rows of image a -> B-operand fragments, resident for the run: 32 codes (24 of 32 bytes) per k-step
+    i32x8 bq[NS][KK];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const int i = min(ibase + s * MF + lr, m_pad - 1);
+        const uint8_t* rp = code + ((size_t)a * m_pad + i) * D + grp * 32;
+#pragma unroll
+        for (int kk = 0; kk < KK; ++kk) {
+            const i32x4 lo = *reinterpret_cast<const i32x4*>(rp + kk * 128);
+            const i32x4 hi = *reinterpret_cast<const i32x4*>(rp + kk * 128 + 16);
+            bq[s][kk] = i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        }
+    }
+
+    float w1[NS], w2[NS];   // the top two of the group maxima
+    int wr[NS];             // the range where the best rose
+#pragma unroll
+    for (int s = 0; s < NS; ++s) { w1[s] = kLow; w2[s] = kLow; wr[s] = 0; }
+
+    __syncthreads();
+
+    for (int blk = 0; blk < nblk; ++blk) {
+        const int cur = blk & 1;
+        if (blk + 1 < nblk)  // next block in flight under the MFMAs
+            S::dma(bcode + (size_t)(blk + 1) * TILE, bhf + (blk + 1) * kJB, lds + (cur ^ 1) * TILE,
+                   kbase + (cur ^ 1) * kJB, wave, lane);
+        const int8_t* tl = lds + cur * TILE;
+        const float* kl = reinterpret_cast<const float*>(kbase + cur * kJB);
+        float rm[NS];
+#pragma unroll
+        for (int jt = 0; jt < JT; ++jt) {
+            if (jt % VG == 0) {
+#pragma unroll
+                for (int s = 0; s < NS; ++s) rm[s] = kLow;
+            }
+            // the lane's four candidate rows of this tile: h_j starts every chain
+            const f32x4 hv = *reinterpret_cast<const f32x4*>(kl + jt * MF + 4 * grp);
+            f32x4 acc[NS];
+#pragma unroll
+            for (int s = 0; s < NS; ++s) acc[s] = hv;
+            const int r = jt * MF + lr;
+#pragma unroll
+            for (int kk = 0; kk < KK; ++kk) {
+                const int c = 2 * (kk * 4 + grp);
+                const i32x4 lo = *reinterpret_cast<const i32x4*>(tl + swz_off<D>(r, c));
+                const i32x4 hi = *reinterpret_cast<const i32x4*>(tl + swz_off<D>(r, c + 1));
+                const i32x8 av = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+#pragma unroll
+                for (int s = 0; s < NS; ++s)
+                    acc[s] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av, bq[s][kk], acc[s], 2, 2, 0, kScale, 0,
+                                                                              kScale);
+            }
+            // 2 VALU per 4 distances; the accumulators' first reader is plain C++ (match_kernel's note)
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                rm[s] = __builtin_fmaxf(__builtin_fmaxf(rm[s], acc[s][0]), acc[s][1]);
+                rm[s] = __builtin_fmaxf(__builtin_fmaxf(rm[s], acc[s][2]), acc[s][3]);
+            }
+            if (jt % VG == VG - 1) {
+                const int rid = blk * (JT / VG) + jt / VG;
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    const bool up = rm[s] > w1[s];   // strict: the earliest range on ties; one compare serves both
+                    wr[s] = up ? rid : wr[s];
+                    w2[s] = __builtin_amdgcn_fmed3f(w1[s], w2[s], rm[s]);
+                    w1[s] = up ? rm[s] : w1[s];
+                }
+            }
+        }
+        __syncthreads();  // drains this wave's DMA; next block visible to all waves
+    }
+
+    int v1[NS], v2[NS];   // integers below 2^24 in magnitude: the conversion is exact
+#pragma unroll
+    for (int s = 0; s < NS; ++s) { v1[s] = (int)w1[s]; v2[s] = (int)w2[s]; }
+    value_only_tail<D, MF, NS, VG, OutT>(v1, v2, wr, g, g + (size_t)b * m_pad * D, h + (size_t)b * m_pad, norms, a, b,
+                                         m_pad, na_rows, ibase, grp, lr, lane, rn2, rd2, out_m, ca);
 }
 
 __global__ void mutual_kernel(int32_t* __restrict__ m0, int32_t* __restrict__ m1, int P, int m_pad) {
@@ -1605,6 +1826,17 @@ extern "C" int sfmhip_desc_quantize(const float* in, int n_img, int m_pad, int d
     return check_launch("quantize_kernel");
 }
 
+extern "C" int sfmhip_desc_quantize_fp6(const float* in, int n_img, int m_pad, int d, const int32_t* n_kpts,
+                                        int8_t* g, uint8_t* code, void* stream) {
+    SFMHIP_REQUIRE(in && g && code && n_kpts, "sfmhip_desc_quantize_fp6: null pointer");
+    SFMHIP_REQUIRE(n_img > 0 && m_pad > 0 && d > 0 && d % 32 == 0, "sfmhip_desc_quantize_fp6: bad shape");
+    const int64_t n_chunks = (int64_t)n_img * m_pad * d / 32;
+    const int grid = (int)std::min<int64_t>((n_chunks + 255) / 256, 4096);
+    hipLaunchKernelGGL(quantize_fp6_kernel, dim3(grid), dim3(256), 0, as_stream(stream), in, n_chunks, d, m_pad,
+                       n_kpts, g, code);
+    return check_launch("quantize_fp6_kernel");
+}
+
 extern "C" int sfmhip_desc_prepare(const int8_t* desc, int n_img, int m_pad, int d,
                                    const int32_t* n_kpts, int32_t* norms, int32_t* keys, void* stream) {
     SFMHIP_REQUIRE(desc && n_kpts && norms && keys, "sfmhip_desc_prepare: null pointer");
@@ -1830,7 +2062,14 @@ static int match_exact_impl(const int8_t* desc, const int32_t* norms, const int3
                             const double* resid_img, int mode, const int32_t* n_kpts, int n_img,
                             int m_pad, int d, const int32_t* pairs, int P, int ratio_num, int ratio_den,
                             OutT* matches0, int32_t* dist1, int32_t* dist2, uint32_t* n_resolved,
-                            void* stream) {
+                            void* stream, const uint8_t* code = nullptr) {
+    // code: the e2m3 codes of desc (the sfmhip_match_pairs_exact_fp6 entries: desc = desc_q = the grid
+    // values g, mode 1, no distance outputs); SFMHIP_MATCH_FP6=0 runs the int8 value-only kernel on g instead
+    const bool fp6 = code && knobs().match_fp6 != 0;
+    if (code) {
+        SFMHIP_REQUIRE(mode == 1 && !dist1 && !dist2 && (d == 128 || d == 256),
+                       "sfmhip_match_pairs_exact_fp6: float mode, d in {128,256}, no distance outputs");
+    }
     SFMHIP_REQUIRE(n_img > 0 && P >= 0, "sfmhip_match_pairs_exact: bad counts");
     SFMHIP_REQUIRE(m_pad > 0 && m_pad % kJB == 0, "sfmhip_match_pairs_exact: m_pad must be a positive multiple of 128");
     SFMHIP_REQUIRE(mode == 0 || mode == 1, "sfmhip_match_pairs_exact: mode must be 0 or 1");
@@ -1866,7 +2105,7 @@ static int match_exact_impl(const int8_t* desc, const int32_t* norms, const int3
     const bool value_only = !dist1 && !dist2;
     const size_t rbytes = 2 * rlist_bytes + rcnt_bytes + roff_bytes + ritem_bytes;   // a multiple of 4
     const size_t hn = value_only ? (size_t)n_img * m_pad : 0;   // the value-only form's h = keys >> 8, behind the rest
-    if (scratch_alloc(&rbuf, rbytes + hn * sizeof(int32_t), s) != hipSuccess) {
+    if (scratch_alloc(&rbuf, rbytes + hn * (fp6 ? 2 : 1) * sizeof(int32_t), s) != hipSuccess) {
         (void)hipGetLastError();
         set_error("sfmhip_match_pairs_exact: scratch allocation failed");
         return SFMHIP_E_HIP;
@@ -1886,14 +2125,20 @@ static int match_exact_impl(const int8_t* desc, const int32_t* norms, const int3
         return check_launch("memset");
     }
     const int rxgrid = n_cu * 2;   // a multiple of 8: every XCD gets the same number of blocks
+    float* hf = nullptr;
     if (hn) {
         int32_t* h = reinterpret_cast<int32_t*>(static_cast<char*>(rbuf) + rbytes);
+        hf = fp6 ? reinterpret_cast<float*>(h + hn) : nullptr;   // the same values in f32, behind h
         hipLaunchKernelGGL(key_values_kernel, dim3(std::min(ceil_div((int64_t)hn, 256), 4096)), dim3(256), 0, s, keys,
-                           (int64_t)hn, h);
+                           (int64_t)hn, h, hf);
         keys = h;
     }
 #define SFMHIP_LAUNCH_EXACT(DD)                                                                                  \
-    if (value_only) {                                                                                             \
+    if (fp6) {                                                                                                    \
+        if constexpr (DD % 128 == 0)                                                                              \
+            hipLaunchKernelGGL((match_fp6_kernel<DD, OutT>), dim3(nwg), dim3(256), 0, s, code, desc, norms, keys, hf,    \
+                               n_kpts, m_pad, pairs, n_iblk, nwg, rn2, rd2, matches0, ca);                        \
+    } else if (value_only) {                                                                                             \
         hipLaunchKernelGGL((match_kernel<DD, 16, 4, 4, true, OutT, kValueOnlyTiles>), dim3(nwg), dim3(256), 0, s, desc, \
                            norms, keys, n_kpts, m_pad, pairs, n_iblk, nwg, rn2, rd2, matches0, dist1, dist2, ca);  \
     } else {                                                                                                      \
@@ -1949,4 +2194,29 @@ extern "C" int sfmhip_match_pairs_exact_i16(const int8_t* desc, const int32_t* n
     return match_exact_impl(desc, norms, keys, desc_q, desc_f, resid_row, resid_img, mode, n_kpts, n_img, m_pad, d,
                             pairs, P, ratio_num, ratio_den, matches0, (int32_t*)nullptr, (int32_t*)nullptr,
                             n_resolved, stream);
+}
+
+// The exact float mode with the FP6 certified filter (DESIGN.md K1''): g and code from
+// sfmhip_desc_quantize_fp6, norms / keys from sfmhip_desc_prepare on g, the residual bounds from
+// sfmhip_desc_residual on (desc_f, g, mode 1).  The same graph as sfmhip_match_pairs_exact.
+extern "C" int sfmhip_match_pairs_exact_fp6(const uint8_t* code, const int8_t* g, const int32_t* norms,
+                                            const int32_t* keys, const float* desc_f, const double* resid_row,
+                                            const double* resid_img, const int32_t* n_kpts, int n_img, int m_pad,
+                                            int d, const int32_t* pairs, int P, int ratio_num, int ratio_den,
+                                            int32_t* matches0, uint32_t* n_resolved, void* stream) {
+    SFMHIP_REQUIRE(code || P == 0, "sfmhip_match_pairs_exact_fp6: null pointer");
+    return match_exact_impl(g, norms, keys, g, desc_f, resid_row, resid_img, 1, n_kpts, n_img, m_pad, d, pairs, P,
+                            ratio_num, ratio_den, matches0, (int32_t*)nullptr, (int32_t*)nullptr, n_resolved, stream,
+                            code);
+}
+
+extern "C" int sfmhip_match_pairs_exact_fp6_i16(const uint8_t* code, const int8_t* g, const int32_t* norms,
+                                                const int32_t* keys, const float* desc_f, const double* resid_row,
+                                                const double* resid_img, const int32_t* n_kpts, int n_img, int m_pad,
+                                                int d, const int32_t* pairs, int P, int ratio_num, int ratio_den,
+                                                int16_t* matches0, uint32_t* n_resolved, void* stream) {
+    SFMHIP_REQUIRE(code || P == 0, "sfmhip_match_pairs_exact_fp6_i16: null pointer");
+    return match_exact_impl(g, norms, keys, g, desc_f, resid_row, resid_img, 1, n_kpts, n_img, m_pad, d, pairs, P,
+                            ratio_num, ratio_den, matches0, (int32_t*)nullptr, (int32_t*)nullptr, n_resolved, stream,
+                            code);
 }

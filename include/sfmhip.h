@@ -160,6 +160,31 @@ int sfmhip_match_pairs_exact_i16(const int8_t* desc, const int32_t* norms, const
                                  int d, const int32_t* pairs, int P, int ratio_num, int ratio_den,
                                  int16_t* matches0, uint32_t* n_resolved, void* stream);
 
+/* The exact float mode with an FP6 (e2m3) certified filter for mode 1, d in
+ * {128, 256} (DESIGN.md K1''): the same graph, the filter's dot products on the
+ * scaled FP6 MFMA.  sfmhip_desc_quantize_fp6: g [n_img][m_pad][d] int8 = the point
+ * of the grid G = {0..15 step 1, 16..30 step 2, 32..60 step 4} (both signs)
+ * nearest to the f32 product 127 * x, clipped at +-60; ties go to the even 6-bit
+ * code; padded rows 0.  code [n_img][m_pad][d] bytes: per 32 elements one 32-byte
+ * chunk, the 6-bit codes (sign << 5 | exponent << 3 | mantissa, bias 1, value
+ * g / 8; g = 0 is code 0) at bits 6 e .. 6 e + 5 of its first 24 bytes, little
+ * endian, the last 8 bytes zero.  d % 32 == 0.
+ * The match entries take norms / keys from sfmhip_desc_prepare on g and the
+ * residual bounds from sfmhip_desc_residual on (desc_f, g, mode 1); v(g) = g / 127.
+ * No distance outputs.  SFMHIP_MATCH_FP6=0 runs the int8 kernel on g instead.   */
+int sfmhip_desc_quantize_fp6(const float* in, int n_img, int m_pad, int d, const int32_t* n_kpts,
+                             int8_t* g, uint8_t* code, void* stream);
+int sfmhip_match_pairs_exact_fp6(const uint8_t* code, const int8_t* g, const int32_t* norms,
+                                 const int32_t* keys, const float* desc_f, const double* resid_row,
+                                 const double* resid_img, const int32_t* n_kpts, int n_img, int m_pad,
+                                 int d, const int32_t* pairs, int P, int ratio_num, int ratio_den,
+                                 int32_t* matches0, uint32_t* n_resolved, void* stream);
+int sfmhip_match_pairs_exact_fp6_i16(const uint8_t* code, const int8_t* g, const int32_t* norms,
+                                     const int32_t* keys, const float* desc_f, const double* resid_row,
+                                     const double* resid_img, const int32_t* n_kpts, int n_img, int m_pad,
+                                     int d, const int32_t* pairs, int P, int ratio_num, int ratio_den,
+                                     int16_t* matches0, uint32_t* n_resolved, void* stream);
+
 /* ---- M2: scipy.cluster.vq.vq (matching.py:27, bow.py:23) ---------------
  * codes[i] = argmin_c sum_k (obs[i,k]-code[c,k])^2 (lowest index on ties),
  * dist[i] = sqrt(min).  f64 throughout.                                      */

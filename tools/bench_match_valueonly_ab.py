@@ -1,13 +1,17 @@
 """Interleaved A/B of builds of libsfmhip.so on the C3 exact-float match step (257 x 4096 x
 256-d, int16 graph: the call dist.match_all_pairs_sharded makes), in one process on one device:
 
-    python tools/bench_match_valueonly_ab.py [--rounds N] OTHER_LIB.so [OTHER_LIB2.so ...]
+    python tools/bench_match_valueonly_ab.py [--rounds N] [--entry NAME] OTHER_LIB.so [OTHER_LIB2.so ...]
 
 The other libraries (e.g. the parent commit's build under another file name) and the tree's
 library all run on the same bank (quantised operands, keys and residual bounds of the tree's
 library), one call each per round in turn, on the full pair list and on the pairs with |a - b| <= 2
 (the overlapping images, where the certificate accepts ~15 % of the rows).  Prints per arm the
-median / min / max step time over the rounds, rows_rescored and a checksum of the match graph."""
+median / min / max step time over the rounds, rows_rescored and a checksum of the match graph.
+--entry sfmhip_match_pairs_exact_fp6_i16 runs the tree's arm through the FP6 entry (the bank's grid
+values, codes and their norms, keys and bounds: DESIGN.md K1''); the other libraries keep
+sfmhip_match_pairs_exact_i16 on the int8 operands, so a parent build without the entry can be the
+other arm."""
 import ctypes
 import hashlib
 import importlib
@@ -27,6 +31,12 @@ rounds = 12
 if args and args[0] == "--rounds":
     rounds, args = int(args[1]), args[2:]
 NAME = "sfmhip_match_pairs_exact_i16"
+TREE_NAME = NAME
+if args and args[0] == "--entry":
+    TREE_NAME, args = args[1], args[2:]
+FP6_NAME = "sfmhip_match_pairs_exact_fp6_i16"
+if TREE_NAME not in (NAME, FP6_NAME):
+    raise SystemExit(f"--entry must be {NAME} or {FP6_NAME}")
 arms = []
 for path in args:
     lib = ctypes.CDLL(os.path.abspath(path))
@@ -50,6 +60,13 @@ for label, pairs in (("full", allp), ("near", near)):
     nres = torch.zeros(1, dtype=torch.int32, device=dev)
 
     def step(lib, out):
+        if lib is abi.lib and TREE_NAME == FP6_NAME:
+            rc = getattr(lib, FP6_NAME)(ptr(bank.code), ptr(bank.g), ptr(bank.gnorms), ptr(bank.gkeys), ptr(bank.x),
+                                        ptr(bank.gerow), ptr(bank.geimg), ptr(bank.n_kpts), bank.n_img, bank.m_pad,
+                                        bank.d, ptr(pr), P, 3, 4, ptr(out), ptr(nres), sp())
+            if rc:
+                raise RuntimeError(f"{FP6_NAME} failed: {rc}")
+            return
         rc = getattr(lib, NAME)(ptr(bank.qm), ptr(bank.norms), ptr(bank.keys), ptr(bank.q), ptr(bank.x),
                                 ptr(bank.erow), ptr(bank.eimg), bank.mode, ptr(bank.n_kpts), bank.n_img, bank.m_pad,
                                 bank.d, ptr(pr), P, 3, 4, ptr(out), ptr(nres), sp())
