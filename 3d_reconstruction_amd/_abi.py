@@ -68,6 +68,7 @@ SIGNATURES = {
     "sfmhip_match_pairs_exact_i16": [_p, _p, _p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _i32, _i32,
                                      _i32, _p, _p, _p],
     "sfmhip_desc_quantize_fp6": [_p, _i32, _i32, _i32, _p, _p, _p, _p],
+    "sfmhip_desc_pack_fp6": [_p, _i32, _i32, _i32, _p, _p],
     "sfmhip_match_pairs_exact_fp6": [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _i32, _i32, _i32, _p, _p,
                                      _p],
     "sfmhip_match_pairs_exact_fp6_i16": [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _i32, _i32, _i32, _p,

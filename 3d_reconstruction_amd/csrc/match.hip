@@ -674,7 +674,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void match_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// match_fp6_kernel (DESIGN.md K1''): the value-only form of match_kernel<D, 16, 4, 4> with the filter's
+// match_fp6_kernel (DESIGN.md K1''): the value-only form of match_kernel (16x16 tiles) with the filter's
 // dot products on v_mfma_scale_f32_16x16x128_f8f6f4 (twice the int8 rate per clock).  The operands are
 // the e2m3 codes of the grid values g (quantize_fp6_kernel; value g / 8) under the unit block scale 2^3
 // (E8M0 byte 130 in every byte of the scale register, so the op_sel byte does not matter): every
@@ -683,21 +683,118 @@ __global__ __launch_bounds__(64 * WAVES, 2) void match_kernel(
 // the order the array sums in, and the identities of the value-only form (match_kernel's comment) hold
 // as they stand, with g in place of q.  The loop's maxima run in f32 (no conversion per distance); the
 // row's top two are converted to int once after the loop (exact) and value_only_tail takes over: its
-// rescan dots the int8 rows g.  Same workgroup shape, LDS ring, XCD remap and ranges as match_kernel;
-// a code row is D bytes (one 32-byte chunk per 32 codes), so Stager and swz_off carry over: a lane's
-// operand for k-step kk is the two 16-byte chunks 2 (4 kk + grp), + 1 of its row.
+// rescan dots the int8 rows g.  Same LDS ring, XCD remap, candidate blocks and ranges as match_kernel.
+//
+// Operands: the dense rows of pack_fp6_kernel (3 D / 4 bytes, no padding).  Slot s = 4 kk + grp of a row
+// (codes 32 s .. 32 s + 31: the 24 bytes a lane gives the MFMA of k-step kk) is a 16-byte low piece at row
+// byte 16 s and an 8-byte high piece at row byte D / 2 + 8 s.  A 128-row block sits in LDS as two planes,
+// [128][D / 2] low pieces and behind them [128][D / 4] high pieces (DenseStager), so a lane's operand is
+// one ds_read_b128 plus one ds_read_b64 that land in adjacent registers: no copies, no padding read.
+typedef int i32x2 __attribute__((ext_vector_type(2)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// One 32-byte code chunk -> the slot's low and high piece of the dense row, one thread per chunk.
+__global__ void pack_fp6_kernel(const uint8_t* __restrict__ code, int64_t n_chunks, int d,
+                                uint8_t* __restrict__ dense) {
+    const int spr = d / 32;   // slots per row
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n_chunks;
+         c += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t row = c / spr;
+        const int s = (int)(c % spr);
+        const uint4 lo = *reinterpret_cast<const uint4*>(code + c * 32);
+        const uint2 hi = *reinterpret_cast<const uint2*>(code + c * 32 + 16);
+        uint8_t* rp = dense + row * (3 * d / 4);
+        *reinterpret_cast<uint4*>(rp + 16 * s) = lo;
+        *reinterpret_cast<uint2*>(rp + d / 2 + 8 * s) = hi;
+    }
+}
+
+// Stage candidate block `src` (128 dense rows) into the two LDS planes of `dst` by LDS-DMA, and its 128
+// chain starts into `kdst`.  The LDS image of a wave-instruction is lane-linear (1 KiB), so both swizzles
+// sit on the per-lane source address, as in Stager.
+//   low plane : 16-byte piece of slot s of row r at  r D/2 + ((s ^ lo_sw(r)) << 4).  ds_read_b128 is
+//     served in the lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31} (+32): with lane = 16 grp + lr the
+//     rows lr = 4..11 of a group read the neighbouring slot s ^ 1, which the term ((lr + 4) >> 3) & 1
+//     undoes; the row term then spreads the group's 16 rows over the 16 16-byte bank slots.
+//   high plane: 8-byte piece of slot s of row r at  LO + r D/4 + (((s >> 1) ^ hi_sw(r)) << 4) + 8 (s & 1).
+//     ds_read_b64 is served in lanes {0-31}, {32-63}: 16 rows x 2 neighbouring slots, which the row term
+//     spreads over the 32 8-byte bank slots.  The swizzle moves 16-byte pairs, the DMA's unit.
+template <int D, int WAVES>
+struct DenseStager {
+    static constexpr int ROW = 3 * D / 4, LB = D / 2, HB = D / 4;   // bytes per dense row, per plane row
+    static constexpr int LO = kJB * LB, TILE = kJB * ROW;           // low plane, both planes
+    static constexpr int CPR = LB / 16, RPB = 256 / LB;             // low: 16-B pieces per row, rows per 256 B
+    static constexpr int UPR = HB / 16, RPH = 256 / HB;             // high: 16-B pairs per row, rows per 256 B
+    static constexpr int NLO = LO / 1024 / WAVES, NHI = (TILE - LO) / 1024 / WAVES;   // wave-instructions per wave
+    static_assert(NLO * WAVES * 1024 == LO && NHI * WAVES * 1024 == TILE - LO && NLO >= 1 && NHI >= 1,
+                  "block / workgroup mismatch");
+    static_assert(RPB * CPR == 16 && RPH * UPR == 16, "a 16-row tile covers every bank once");
+
+    __device__ static int lo_sw(int r) { return ((((r & 15) + 4) >> 3) & 1) ^ ((r / RPB) % CPR); }
+    __device__ static int hi_sw(int r) { return (r / RPH) % UPR; }
+    __device__ static int lo_off(int r, int s) { return r * LB + ((s ^ lo_sw(r)) << 4); }
+    __device__ static int hi_off(int r, int s) { return LO + r * HB + ((((s >> 1) ^ hi_sw(r)) << 4) | ((s & 1) << 3)); }
+
+    __device__ static void dma(const uint8_t* src, const int32_t* ksrc, int8_t* dst, int32_t* kdst, int wave,
+                               int lane) {
+#pragma unroll
+        for (int u = 0; u < NLO; ++u) {
+            const int ins = wave * NLO + u;
+            const int r = ins * (1024 / LB) + lane / CPR;
+            const int c = (lane % CPR) ^ lo_sw(r);
+            __builtin_amdgcn_global_load_lds(
+                (__attribute__((address_space(1))) void*)(src + (size_t)r * ROW + c * 16),
+                (__attribute__((address_space(3))) void*)(dst + ins * 1024), 16, 0, 0);
+        }
+#pragma unroll
+        for (int u = 0; u < NHI; ++u) {
+            const int ins = wave * NHI + u;
+            const int r = ins * (1024 / HB) + lane / UPR;
+            const int c = (lane % UPR) ^ hi_sw(r);
+            __builtin_amdgcn_global_load_lds(
+                (__attribute__((address_space(1))) void*)(src + (size_t)r * ROW + LB + c * 16),
+                (__attribute__((address_space(3))) void*)(dst + LO + ins * 1024), 16, 0, 0);
+        }
+        if (wave == WAVES - 1) {  // 128 chain starts = 2 x (64 lanes x 4 B)
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+                __builtin_amdgcn_global_load_lds(
+                    (__attribute__((address_space(1))) void*)(ksrc + u * 64 + lane),
+                    (__attribute__((address_space(3))) void*)(kdst + u * 64), 4, 0, 0);
+        }
+    }
+};
+
+// The operand's high piece.  A plain 8-byte read is paired with its neighbour (ds_read2st64_b64) and the
+// pieces then need copies into the MFMA's register tuple; a volatile LDS read stays a ds_read_b64 that the
+// compiler still counts in its s_waitcnt.
+__device__ __forceinline__ i32x2 lds_read_b64(const int8_t* p) {
+    return *(const volatile __attribute__((address_space(3))) i32x2*)p;
+}
+
+struct Fp6Operand {   // 32 codes: 24 bytes in 6 registers
+    i32x4 lo;
+    i32x2 hi;
+    __device__ i32x8 tuple() const { return i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], 0, 0}; }
+};
+
+// 8 query tiles of 16 rows per wave, 4 waves: 512 query rows per workgroup.  A candidate operand read from
+// LDS feeds 8 MFMAs.  Measured on C3 against 4 tiles x 4 waves and 8 tiles x 2 waves (256 rows per
+// workgroup): 53.1 / 58.0 / 64.0 ms (profiles/r10/match_fp6_dense_ab.txt)
+constexpr int kFp6Tiles = 8;
+constexpr int kFp6Waves = 4;
+
 template <int D, typename OutT>
-__global__ __launch_bounds__(256, 2) void match_fp6_kernel(
-    const uint8_t* __restrict__ code, const int8_t* __restrict__ g, const int32_t* __restrict__ norms,
+__global__ __launch_bounds__(64 * kFp6Waves, 2) void match_fp6_kernel(
+    const uint8_t* __restrict__ dense, const int8_t* __restrict__ g, const int32_t* __restrict__ norms,
     const int32_t* __restrict__ h, const float* __restrict__ hf, const int32_t* __restrict__ nk, int m_pad,
     const int32_t* __restrict__ pairs, int n_iblk, int nwg, long long rn2, long long rd2,
     OutT* __restrict__ m0, CertArgs ca) {
-    constexpr int MF = 16, NS = 4, WAVES = 4, VG = kValueOnlyTiles;
+    constexpr int MF = 16, NS = kFp6Tiles, WAVES = kFp6Waves, VG = kValueOnlyTiles;
     static_assert(D % 128 == 0, "one scaled MFMA takes 128 elements of k");
-    using S = Stager<D, WAVES>;
+    static_assert(NS % 4 == 0, "value_only_tail takes four query tiles at a time");
+    using S = DenseStager<D, WAVES>;
     constexpr int KK = D / 128;                     // scaled MFMAs per output tile
     constexpr int TILE = S::TILE;
     constexpr int NT = 64 * WAVES;
@@ -724,25 +821,31 @@ __global__ __launch_bounds__(256, 2) void match_fp6_kernel(
         return;
     }
 
-    const int8_t* bcode = reinterpret_cast<const int8_t*>(code) + (size_t)b * m_pad * D;
+    const uint8_t* bdense = dense + (size_t)b * m_pad * S::ROW;
     const int32_t* bhf = reinterpret_cast<const int32_t*>(hf) + (size_t)b * m_pad;   // f32 bits through the key DMA
     const int nblk = (nb_rows + kJB - 1) / kJB;
     int32_t* kbase = reinterpret_cast<int32_t*>(lds + 2 * TILE);
 
-    S::dma(bcode, bhf, lds, kbase, wave, lane);  // block 0 in flight
+    S::dma(bdense, bhf, lds, kbase, wave, lane);  // block 0 in flight
 
-    // Query rows of image a -> B-operand fragments, resident for the run: 32 codes (24 of 32 bytes) per k-step
-    i32x8 bq[NS][KK];
+    // Query rows of image a -> B-operand fragments, resident for the run: 32 codes in 6 registers per k-step
+    Fp6Operand bq[NS][KK];
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
         const int i = min(ibase + s * MF + lr, m_pad - 1);
-        const uint8_t* rp = code + ((size_t)a * m_pad + i) * D + grp * 32;
+        const uint8_t* rp = dense + ((size_t)a * m_pad + i) * S::ROW;
 #pragma unroll
         for (int kk = 0; kk < KK; ++kk) {
-            const i32x4 lo = *reinterpret_cast<const i32x4*>(rp + kk * 128);
-            const i32x4 hi = *reinterpret_cast<const i32x4*>(rp + kk * 128 + 16);
-            bq[s][kk] = i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+            bq[s][kk].lo = *reinterpret_cast<const i32x4*>(rp + 16 * (kk * 4 + grp));
+            bq[s][kk].hi = *reinterpret_cast<const i32x2*>(rp + S::LB + 8 * (kk * 4 + grp));
         }
+    }
+    // the lane's piece offsets inside a 16-row candidate tile (the swizzles depend on the row only mod 16)
+    int lo_b[KK], hi_b[KK];
+#pragma unroll
+    for (int kk = 0; kk < KK; ++kk) {
+        lo_b[kk] = S::lo_off(lr, kk * 4 + grp);
+        hi_b[kk] = S::hi_off(lr, kk * 4 + grp);
     }
 
     float w1[NS], w2[NS];   // the top two of the group maxima
@@ -755,7 +858,7 @@ __global__ __launch_bounds__(256, 2) void match_fp6_kernel(
     for (int blk = 0; blk < nblk; ++blk) {
         const int cur = blk & 1;
         if (blk + 1 < nblk)  // next block in flight under the MFMAs
-            S::dma(bcode + (size_t)(blk + 1) * TILE, bhf + (blk + 1) * kJB, lds + (cur ^ 1) * TILE,
+            S::dma(bdense + (size_t)(blk + 1) * TILE, bhf + (blk + 1) * kJB, lds + (cur ^ 1) * TILE,
                    kbase + (cur ^ 1) * kJB, wave, lane);
         const int8_t* tl = lds + cur * TILE;
         const float* kl = reinterpret_cast<const float*>(kbase + cur * kJB);
@@ -771,17 +874,15 @@ __global__ __launch_bounds__(256, 2) void match_fp6_kernel(
             f32x4 acc[NS];
 #pragma unroll
             for (int s = 0; s < NS; ++s) acc[s] = hv;
-            const int r = jt * MF + lr;
 #pragma unroll
             for (int kk = 0; kk < KK; ++kk) {
-                const int c = 2 * (kk * 4 + grp);
-                const i32x4 lo = *reinterpret_cast<const i32x4*>(tl + swz_off<D>(r, c));
-                const i32x4 hi = *reinterpret_cast<const i32x4*>(tl + swz_off<D>(r, c + 1));
-                const i32x8 av = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                Fp6Operand av;
+                av.lo = *reinterpret_cast<const i32x4*>(tl + lo_b[kk] + jt * MF * S::LB);
+                av.hi = lds_read_b64(tl + hi_b[kk] + jt * MF * S::HB);
 #pragma unroll
                 for (int s = 0; s < NS; ++s)
-                    acc[s] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av, bq[s][kk], acc[s], 2, 2, 0, kScale, 0,
-                                                                              kScale);
+                    acc[s] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av.tuple(), bq[s][kk].tuple(), acc[s], 2, 2,
+                                                                              0, kScale, 0, kScale);
             }
             // 2 VALU per 4 distances; the accumulators' first reader is plain C++ (match_kernel's note)
 #pragma unroll
@@ -803,11 +904,15 @@ __global__ __launch_bounds__(256, 2) void match_fp6_kernel(
         __syncthreads();  // drains this wave's DMA; next block visible to all waves
     }
 
-    int v1[NS], v2[NS];   // integers below 2^24 in magnitude: the conversion is exact
+    // value_only_tail decides 64 query rows (four tiles, one per lane group) per call
 #pragma unroll
-    for (int s = 0; s < NS; ++s) { v1[s] = (int)w1[s]; v2[s] = (int)w2[s]; }
-    value_only_tail<D, MF, NS, VG, OutT>(v1, v2, wr, g, g + (size_t)b * m_pad * D, h + (size_t)b * m_pad, norms, a, b,
-                                         m_pad, na_rows, ibase, grp, lr, lane, rn2, rd2, out_m, ca);
+    for (int q = 0; q < NS / 4; ++q) {
+        int v1[4], v2[4], vr[4];   // integers below 2^24 in magnitude: the conversion is exact
+#pragma unroll
+        for (int s = 0; s < 4; ++s) { v1[s] = (int)w1[4 * q + s]; v2[s] = (int)w2[4 * q + s]; vr[s] = wr[4 * q + s]; }
+        value_only_tail<D, MF, 4, VG, OutT>(v1, v2, vr, g, g + (size_t)b * m_pad * D, h + (size_t)b * m_pad, norms, a, b,
+                                            m_pad, na_rows, ibase + q * 4 * MF, grp, lr, lane, rn2, rd2, out_m, ca);
+    }
 }
 
 __global__ void mutual_kernel(int32_t* __restrict__ m0, int32_t* __restrict__ m1, int P, int m_pad) {
@@ -1837,6 +1942,15 @@ extern "C" int sfmhip_desc_quantize_fp6(const float* in, int n_img, int m_pad, i
     return check_launch("quantize_fp6_kernel");
 }
 
+extern "C" int sfmhip_desc_pack_fp6(const uint8_t* code, int n_img, int m_pad, int d, uint8_t* dense, void* stream) {
+    SFMHIP_REQUIRE(code && dense, "sfmhip_desc_pack_fp6: null pointer");
+    SFMHIP_REQUIRE(n_img > 0 && m_pad > 0 && d > 0 && d % 64 == 0, "sfmhip_desc_pack_fp6: bad shape");
+    const int64_t n_chunks = (int64_t)n_img * m_pad * d / 32;
+    const int grid = (int)std::min<int64_t>((n_chunks + 255) / 256, 4096);
+    hipLaunchKernelGGL(pack_fp6_kernel, dim3(grid), dim3(256), 0, as_stream(stream), code, n_chunks, d, dense);
+    return check_launch("pack_fp6_kernel");
+}
+
 extern "C" int sfmhip_desc_prepare(const int8_t* desc, int n_img, int m_pad, int d,
                                    const int32_t* n_kpts, int32_t* norms, int32_t* keys, void* stream) {
     SFMHIP_REQUIRE(desc && n_kpts && norms && keys, "sfmhip_desc_prepare: null pointer");
@@ -2062,11 +2176,12 @@ static int match_exact_impl(const int8_t* desc, const int32_t* norms, const int3
                             const double* resid_img, int mode, const int32_t* n_kpts, int n_img,
                             int m_pad, int d, const int32_t* pairs, int P, int ratio_num, int ratio_den,
                             OutT* matches0, int32_t* dist1, int32_t* dist2, uint32_t* n_resolved,
-                            void* stream, const uint8_t* code = nullptr) {
-    // code: the e2m3 codes of desc (the sfmhip_match_pairs_exact_fp6 entries: desc = desc_q = the grid
-    // values g, mode 1, no distance outputs); SFMHIP_MATCH_FP6=0 runs the int8 value-only kernel on g instead
-    const bool fp6 = code && knobs().match_fp6 != 0;
-    if (code) {
+                            void* stream, const uint8_t* dense = nullptr) {
+    // dense: the packed e2m3 codes of desc (sfmhip_desc_pack_fp6; the sfmhip_match_pairs_exact_fp6 entries:
+    // desc = desc_q = the grid values g, mode 1, no distance outputs); SFMHIP_MATCH_FP6=0 runs the int8
+    // value-only kernel on g instead
+    const bool fp6 = dense && knobs().match_fp6 != 0;
+    if (dense) {
         SFMHIP_REQUIRE(mode == 1 && !dist1 && !dist2 && (d == 128 || d == 256),
                        "sfmhip_match_pairs_exact_fp6: float mode, d in {128,256}, no distance outputs");
     }
@@ -2080,7 +2195,8 @@ static int match_exact_impl(const int8_t* desc, const int32_t* norms, const int3
     if (P == 0) return SFMHIP_OK;
     SFMHIP_REQUIRE(desc && norms && keys && desc_q && desc_f && resid_row && resid_img && n_kpts && pairs && matches0,
                    "sfmhip_match_pairs_exact: null pointer");
-    constexpr int IB = 256;   // match_kernel's query rows per workgroup (16x16 tiles, 4 per wave, 4 waves)
+    // query rows per workgroup: match_kernel 16x16 tiles, 4 per wave, 4 waves; match_fp6_kernel its own
+    const int IB = fp6 ? 16 * kFp6Tiles * kFp6Waves : 256;
     const int n_iblk = ceil_div(m_pad, IB);
     const int64_t nwg64 = (int64_t)P * n_iblk;
     SFMHIP_REQUIRE(nwg64 < INT_MAX, "sfmhip_match_pairs_exact: too many pairs for one launch");
@@ -2136,8 +2252,8 @@ static int match_exact_impl(const int8_t* desc, const int32_t* norms, const int3
 #define SFMHIP_LAUNCH_EXACT(DD)                                                                                  \
     if (fp6) {                                                                                                    \
         if constexpr (DD % 128 == 0)                                                                              \
-            hipLaunchKernelGGL((match_fp6_kernel<DD, OutT>), dim3(nwg), dim3(256), 0, s, code, desc, norms, keys, hf,    \
-                               n_kpts, m_pad, pairs, n_iblk, nwg, rn2, rd2, matches0, ca);                        \
+            hipLaunchKernelGGL((match_fp6_kernel<DD, OutT>), dim3(nwg), dim3(64 * kFp6Waves), 0, s, dense, desc, norms,  \
+                               keys, hf, n_kpts, m_pad, pairs, n_iblk, nwg, rn2, rd2, matches0, ca);              \
     } else if (value_only) {                                                                                             \
         hipLaunchKernelGGL((match_kernel<DD, 16, 4, 4, true, OutT, kValueOnlyTiles>), dim3(nwg), dim3(256), 0, s, desc, \
                            norms, keys, n_kpts, m_pad, pairs, n_iblk, nwg, rn2, rd2, matches0, dist1, dist2, ca);  \
@@ -2196,27 +2312,27 @@ extern "C" int sfmhip_match_pairs_exact_i16(const int8_t* desc, const int32_t* n
                             n_resolved, stream);
 }
 
-// The exact float mode with the FP6 certified filter (DESIGN.md K1''): g and code from
-// sfmhip_desc_quantize_fp6, norms / keys from sfmhip_desc_prepare on g, the residual bounds from
+// The exact float mode with the FP6 certified filter (DESIGN.md K1''): g from sfmhip_desc_quantize_fp6, dense
+// from sfmhip_desc_pack_fp6 on its codes, norms / keys from sfmhip_desc_prepare on g, the residual bounds from
 // sfmhip_desc_residual on (desc_f, g, mode 1).  The same graph as sfmhip_match_pairs_exact.
-extern "C" int sfmhip_match_pairs_exact_fp6(const uint8_t* code, const int8_t* g, const int32_t* norms,
+extern "C" int sfmhip_match_pairs_exact_fp6(const uint8_t* dense, const int8_t* g, const int32_t* norms,
                                             const int32_t* keys, const float* desc_f, const double* resid_row,
                                             const double* resid_img, const int32_t* n_kpts, int n_img, int m_pad,
                                             int d, const int32_t* pairs, int P, int ratio_num, int ratio_den,
                                             int32_t* matches0, uint32_t* n_resolved, void* stream) {
-    SFMHIP_REQUIRE(code || P == 0, "sfmhip_match_pairs_exact_fp6: null pointer");
+    SFMHIP_REQUIRE(dense || P == 0, "sfmhip_match_pairs_exact_fp6: null pointer");
     return match_exact_impl(g, norms, keys, g, desc_f, resid_row, resid_img, 1, n_kpts, n_img, m_pad, d, pairs, P,
                             ratio_num, ratio_den, matches0, (int32_t*)nullptr, (int32_t*)nullptr, n_resolved, stream,
-                            code);
+                            dense);
 }
 
-extern "C" int sfmhip_match_pairs_exact_fp6_i16(const uint8_t* code, const int8_t* g, const int32_t* norms,
+extern "C" int sfmhip_match_pairs_exact_fp6_i16(const uint8_t* dense, const int8_t* g, const int32_t* norms,
                                                 const int32_t* keys, const float* desc_f, const double* resid_row,
                                                 const double* resid_img, const int32_t* n_kpts, int n_img, int m_pad,
                                                 int d, const int32_t* pairs, int P, int ratio_num, int ratio_den,
                                                 int16_t* matches0, uint32_t* n_resolved, void* stream) {
-    SFMHIP_REQUIRE(code || P == 0, "sfmhip_match_pairs_exact_fp6_i16: null pointer");
+    SFMHIP_REQUIRE(dense || P == 0, "sfmhip_match_pairs_exact_fp6_i16: null pointer");
     return match_exact_impl(g, norms, keys, g, desc_f, resid_row, resid_img, 1, n_kpts, n_img, m_pad, d, pairs, P,
                             ratio_num, ratio_den, matches0, (int32_t*)nullptr, (int32_t*)nullptr, n_resolved, stream,
-                            code);
+                            dense);
 }

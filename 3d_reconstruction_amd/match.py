@@ -112,9 +112,11 @@ class DescriptorBank:
             call("sfmhip_desc_residual", ptr(self.x), ptr(self.q), self.n_img, self.m_pad, self.d, ptr(self.n_kpts),
                  self.mode, ptr(self.erow), ptr(self.eimg), stream_ptr())
             self._nres = torch.zeros(1, dtype=torch.int32, device=q.device)
-        # FP6 certified filter (DESIGN.md K1''): the grid values g, their e2m3 codes and g's norms, keys and
-        # residual bounds, built once (the descriptors do not change between match calls); +2 bytes per element
+        # FP6 certified filter (DESIGN.md K1''): the grid values g, their e2m3 codes, the dense operand rows the
+        # kernel reads and g's norms, keys and residual bounds, built once (the descriptors do not change between
+        # match calls); +2.75 bytes per element
         self.code = None
+        self.dense = None
         if x is not None and self.mode == MODE_FLOAT and self.d % 128 == 0:
             self.g = torch.empty_like(self.q)
             self.code = torch.empty(self.q.shape, dtype=torch.uint8, device=q.device)
@@ -122,6 +124,8 @@ class DescriptorBank:
             self.gerow, self.geimg = torch.empty_like(self.erow), torch.empty_like(self.eimg)
             call("sfmhip_desc_quantize_fp6", ptr(self.x), self.n_img, self.m_pad, self.d, ptr(self.n_kpts),
                  ptr(self.g), ptr(self.code), stream_ptr())
+            self.dense = torch.empty((self.n_img, self.m_pad, 3 * self.d // 4), dtype=torch.uint8, device=q.device)
+            call("sfmhip_desc_pack_fp6", ptr(self.code), self.n_img, self.m_pad, self.d, ptr(self.dense), stream_ptr())
             call("sfmhip_desc_prepare", ptr(self.g), self.n_img, self.m_pad, self.d, ptr(self.n_kpts),
                  ptr(self.gnorms), ptr(self.gkeys), stream_ptr())
             call("sfmhip_desc_residual", ptr(self.x), ptr(self.g), self.n_img, self.m_pad, self.d, ptr(self.n_kpts),
@@ -223,8 +227,8 @@ class DescriptorBank:
     def _launch(self, pr, num, den, m0, d1, d2, exact: bool | None = None):
         exact = getattr(self, "_exact_now", False) if exact is None else exact
         i16 = m0.dtype == torch.int16
-        if exact and d1 is None and self.code is not None:   # the FP6 filter (SFMHIP_MATCH_FP6=0: int8 on g)
-            call("sfmhip_match_pairs_exact_fp6_i16" if i16 else "sfmhip_match_pairs_exact_fp6", ptr(self.code),
+        if exact and d1 is None and self.dense is not None:   # the FP6 filter (SFMHIP_MATCH_FP6=0: int8 on g)
+            call("sfmhip_match_pairs_exact_fp6_i16" if i16 else "sfmhip_match_pairs_exact_fp6", ptr(self.dense),
                  ptr(self.g), ptr(self.gnorms), ptr(self.gkeys), ptr(self.x), ptr(self.gerow), ptr(self.geimg),
                  ptr(self.n_kpts), self.n_img, self.m_pad, self.d, ptr(pr), int(pr.shape[0]), num, den, ptr(m0),
                  ptr(self._nres), stream_ptr())

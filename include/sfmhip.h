@@ -169,17 +169,27 @@ int sfmhip_match_pairs_exact_i16(const int8_t* desc, const int32_t* norms, const
  * chunk, the 6-bit codes (sign << 5 | exponent << 3 | mantissa, bias 1, value
  * g / 8; g = 0 is code 0) at bits 6 e .. 6 e + 5 of its first 24 bytes, little
  * endian, the last 8 bytes zero.  d % 32 == 0.
- * The match entries take norms / keys from sfmhip_desc_prepare on g and the
- * residual bounds from sfmhip_desc_residual on (desc_f, g, mode 1); v(g) = g / 127.
+ * sfmhip_desc_pack_fp6: the operand rows the match kernel reads, built once per
+ * bank from `code`.  dense [n_img][m_pad][3 d / 4] bytes, no padding.  Slot s
+ * (s = 0 .. d / 32 - 1) of a row is the 24 code bytes of the row's chunk s (codes
+ * 32 s .. 32 s + 31), split in two naturally aligned pieces:
+ *   low  piece, 16 bytes = chunk bytes 0 .. 15,  at row byte 16 s;
+ *   high piece,  8 bytes = chunk bytes 16 .. 23, at row byte d / 2 + 8 s.
+ * So a row is its d / 32 low pieces (d / 2 bytes) followed by its d / 32 high
+ * pieces (d / 4 bytes): 192 bytes at d = 256, 96 at d = 128.  d % 64 == 0.
+ * The match entries take `dense` as their first pointer, norms / keys from
+ * sfmhip_desc_prepare on g and the residual bounds from sfmhip_desc_residual on
+ * (desc_f, g, mode 1); v(g) = g / 127.
  * No distance outputs.  SFMHIP_MATCH_FP6=0 runs the int8 kernel on g instead.   */
 int sfmhip_desc_quantize_fp6(const float* in, int n_img, int m_pad, int d, const int32_t* n_kpts,
                              int8_t* g, uint8_t* code, void* stream);
-int sfmhip_match_pairs_exact_fp6(const uint8_t* code, const int8_t* g, const int32_t* norms,
+int sfmhip_desc_pack_fp6(const uint8_t* code, int n_img, int m_pad, int d, uint8_t* dense, void* stream);
+int sfmhip_match_pairs_exact_fp6(const uint8_t* dense, const int8_t* g, const int32_t* norms,
                                  const int32_t* keys, const float* desc_f, const double* resid_row,
                                  const double* resid_img, const int32_t* n_kpts, int n_img, int m_pad,
                                  int d, const int32_t* pairs, int P, int ratio_num, int ratio_den,
                                  int32_t* matches0, uint32_t* n_resolved, void* stream);
-int sfmhip_match_pairs_exact_fp6_i16(const uint8_t* code, const int8_t* g, const int32_t* norms,
+int sfmhip_match_pairs_exact_fp6_i16(const uint8_t* dense, const int8_t* g, const int32_t* norms,
                                      const int32_t* keys, const float* desc_f, const double* resid_row,
                                      const double* resid_img, const int32_t* n_kpts, int n_img, int m_pad,
                                      int d, const int32_t* pairs, int P, int ratio_num, int ratio_den,

@@ -1,7 +1,7 @@
 """Interleaved A/B of builds of libsfmhip.so on the C3 exact-float match step (257 x 4096 x
 256-d, int16 graph: the call dist.match_all_pairs_sharded makes), in one process on one device:
 
-    python tools/bench_match_valueonly_ab.py [--rounds N] [--entry NAME] OTHER_LIB.so [OTHER_LIB2.so ...]
+    python tools/bench_match_valueonly_ab.py [--rounds N] [--entry NAME] [--other-entry NAME] OTHER_LIB.so [...]
 
 The other libraries (e.g. the parent commit's build under another file name) and the tree's
 library all run on the same bank (quantised operands, keys and residual bounds of the tree's
@@ -11,7 +11,10 @@ median / min / max step time over the rounds, rows_rescored and a checksum of th
 --entry sfmhip_match_pairs_exact_fp6_i16 runs the tree's arm through the FP6 entry (the bank's grid
 values, codes and their norms, keys and bounds: DESIGN.md K1''); the other libraries keep
 sfmhip_match_pairs_exact_i16 on the int8 operands, so a parent build without the entry can be the
-other arm."""
+other arm, unless --other-entry sfmhip_match_pairs_exact_fp6_i16 sends them through their FP6 entry
+too.  An FP6 arm gets the operand array its library reads: the dense rows (bank.dense) when the library
+exports sfmhip_desc_pack_fp6, the 32-byte chunks of the quantiser (bank.code) when it does not — a
+parent build from before the dense layout."""
 import ctypes
 import hashlib
 import importlib
@@ -34,14 +37,17 @@ NAME = "sfmhip_match_pairs_exact_i16"
 TREE_NAME = NAME
 if args and args[0] == "--entry":
     TREE_NAME, args = args[1], args[2:]
+OTHER_NAME = NAME
+if args and args[0] == "--other-entry":
+    OTHER_NAME, args = args[1], args[2:]
 FP6_NAME = "sfmhip_match_pairs_exact_fp6_i16"
-if TREE_NAME not in (NAME, FP6_NAME):
-    raise SystemExit(f"--entry must be {NAME} or {FP6_NAME}")
+if TREE_NAME not in (NAME, FP6_NAME) or OTHER_NAME not in (NAME, FP6_NAME):
+    raise SystemExit(f"--entry and --other-entry must be {NAME} or {FP6_NAME}")
 arms = []
 for path in args:
     lib = ctypes.CDLL(os.path.abspath(path))
-    getattr(lib, NAME).argtypes = abi.SIGNATURES[NAME]
-    getattr(lib, NAME).restype = ctypes.c_int
+    getattr(lib, OTHER_NAME).argtypes = abi.SIGNATURES[OTHER_NAME]
+    getattr(lib, OTHER_NAME).restype = ctypes.c_int
     arms.append((os.path.basename(path), lib))
 arms.append(("tree", abi.lib))
 
@@ -60,8 +66,9 @@ for label, pairs in (("full", allp), ("near", near)):
     nres = torch.zeros(1, dtype=torch.int32, device=dev)
 
     def step(lib, out):
-        if lib is abi.lib and TREE_NAME == FP6_NAME:
-            rc = getattr(lib, FP6_NAME)(ptr(bank.code), ptr(bank.g), ptr(bank.gnorms), ptr(bank.gkeys), ptr(bank.x),
+        if (TREE_NAME if lib is abi.lib else OTHER_NAME) == FP6_NAME:
+            operands = bank.dense if hasattr(lib, "sfmhip_desc_pack_fp6") else bank.code
+            rc = getattr(lib, FP6_NAME)(ptr(operands), ptr(bank.g), ptr(bank.gnorms), ptr(bank.gkeys), ptr(bank.x),
                                         ptr(bank.gerow), ptr(bank.geimg), ptr(bank.n_kpts), bank.n_img, bank.m_pad,
                                         bank.d, ptr(pr), P, 3, 4, ptr(out), ptr(nres), sp())
             if rc:
