@@ -20,6 +20,7 @@
 //     merge into (best key, best index, second key) with explicit index order.
 //   * nothing of the M x N distance matrix is ever written.
 #include "common.h"
+#include "fp6_sched.h"
 #include <climits>
 #include <cstdlib>
 
@@ -684,6 +685,8 @@ __global__ __launch_bounds__(64 * WAVES, 2) void match_kernel(
 // as they stand, with g in place of q.  The loop's maxima run in f32 (no conversion per distance); the
 // row's top two are converted to int once after the loop (exact) and value_only_tail takes over: its
 // rescan dots the int8 rows g.  Same LDS ring, XCD remap, candidate blocks and ranges as match_kernel.
+// The block loop is software-pipelined by one tile (fp6_sched.h): a tile's maxima and a range's merge
+// issue in the gaps between the following MFMAs, in an order the source pins.
 //
 // Operands: the dense rows of pack_fp6_kernel (3 D / 4 bytes, no padding).  Slot s = 4 kk + grp of a row
 // (codes 32 s .. 32 s + 31: the 24 bytes a lane gives the MFMA of k-step kk) is a 16-byte low piece at row
@@ -736,31 +739,52 @@ struct DenseStager {
     __device__ static int lo_off(int r, int s) { return r * LB + ((s ^ lo_sw(r)) << 4); }
     __device__ static int hi_off(int r, int s) { return LO + r * HB + ((((s >> 1) ^ hi_sw(r)) << 4) | ((s & 1) << 3)); }
 
-    __device__ static void dma(const uint8_t* src, const int32_t* ksrc, int8_t* dst, int32_t* kdst, int wave,
-                               int lane) {
+    // The lane's source byte offset inside a block for each of its wave's DMA instructions: computed once,
+    // so that a block's addresses are a wave-uniform base (scalar unit) plus these.
+    struct Lanes {
+        unsigned lo[NLO], hi[NHI], key;
+    };
+    __device__ static Lanes lanes(int wave, int lane) {
+        Lanes l;
 #pragma unroll
         for (int u = 0; u < NLO; ++u) {
-            const int ins = wave * NLO + u;
-            const int r = ins * (1024 / LB) + lane / CPR;
-            const int c = (lane % CPR) ^ lo_sw(r);
-            __builtin_amdgcn_global_load_lds(
-                (__attribute__((address_space(1))) void*)(src + (size_t)r * ROW + c * 16),
-                (__attribute__((address_space(3))) void*)(dst + ins * 1024), 16, 0, 0);
+            const int r = (wave * NLO + u) * (1024 / LB) + lane / CPR;
+            l.lo[u] = (unsigned)(r * ROW + (((lane % CPR) ^ lo_sw(r)) << 4));
         }
 #pragma unroll
         for (int u = 0; u < NHI; ++u) {
-            const int ins = wave * NHI + u;
-            const int r = ins * (1024 / HB) + lane / UPR;
-            const int c = (lane % UPR) ^ hi_sw(r);
+            const int r = (wave * NHI + u) * (1024 / HB) + lane / UPR;
+            l.hi[u] = (unsigned)(r * ROW + LB + (((lane % UPR) ^ hi_sw(r)) << 4));
+        }
+        l.key = (unsigned)(lane * 4);
+        return l;
+    }
+
+    __device__ static void dma(const uint8_t* src, const int32_t* ksrc, int8_t* dst, int32_t* kdst, int wave,
+                               const Lanes& l) {
+        // the offsets pass through an empty asm so that their widening to 64 bits stays beside the load: the
+        // instruction then takes the scalar base and the 32-bit lane offset as they are (no vector address add)
+#pragma unroll
+        for (int u = 0; u < NLO; ++u) {
+            unsigned o = l.lo[u];
+            asm volatile("" : "+v"(o));
+            __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)(src + o),
+                                             (__attribute__((address_space(3))) void*)(dst + (wave * NLO + u) * 1024),
+                                             16, 0, 0);
+        }
+#pragma unroll
+        for (int u = 0; u < NHI; ++u) {
+            unsigned o = l.hi[u];
+            asm volatile("" : "+v"(o));
             __builtin_amdgcn_global_load_lds(
-                (__attribute__((address_space(1))) void*)(src + (size_t)r * ROW + LB + c * 16),
-                (__attribute__((address_space(3))) void*)(dst + LO + ins * 1024), 16, 0, 0);
+                (__attribute__((address_space(1))) void*)(src + o),
+                (__attribute__((address_space(3))) void*)(dst + LO + (wave * NHI + u) * 1024), 16, 0, 0);
         }
         if (wave == WAVES - 1) {  // 128 chain starts = 2 x (64 lanes x 4 B)
 #pragma unroll
             for (int u = 0; u < 2; ++u)
                 __builtin_amdgcn_global_load_lds(
-                    (__attribute__((address_space(1))) void*)(ksrc + u * 64 + lane),
+                    (__attribute__((address_space(1))) void*)(reinterpret_cast<const uint8_t*>(ksrc + u * 64) + l.key),
                     (__attribute__((address_space(3))) void*)(kdst + u * 64), 4, 0, 0);
         }
     }
@@ -796,6 +820,10 @@ __global__ __launch_bounds__(64 * kFp6Waves, 2) void match_fp6_kernel(
     static_assert(NS % 4 == 0, "value_only_tail takes four query tiles at a time");
     using S = DenseStager<D, WAVES>;
     constexpr int KK = D / 128;                     // scaled MFMAs per output tile
+    using SC = Fp6Sched<KK, NS>;
+    static_assert(kJB / MF == 2 * VG, "two ranges per block: the range maxima alternate between two sets");
+    static_assert(SC::merge(VG * SC::MPT, 0) == -1, "a range's gaps hold the previous range's merge");
+    static_assert(SC::merge_ready(), "a chain's merge starts behind its last maximum");
     constexpr int TILE = S::TILE;
     constexpr int NT = 64 * WAVES;
     constexpr int IW = MF * NS, IB = IW * WAVES;
@@ -826,7 +854,8 @@ __global__ __launch_bounds__(64 * kFp6Waves, 2) void match_fp6_kernel(
     const int nblk = (nb_rows + kJB - 1) / kJB;
     int32_t* kbase = reinterpret_cast<int32_t*>(lds + 2 * TILE);
 
-    S::dma(bdense, bhf, lds, kbase, wave, lane);  // block 0 in flight
+    const typename S::Lanes dl = S::lanes(wave, lane);
+    S::dma(bdense, bhf, lds, kbase, wave, dl);  // block 0 in flight
 
     // Query rows of image a -> B-operand fragments, resident for the run: 32 codes in 6 registers per k-step
     Fp6Operand bq[NS][KK];
@@ -850,59 +879,109 @@ __global__ __launch_bounds__(64 * kFp6Waves, 2) void match_fp6_kernel(
 
     float w1[NS], w2[NS];   // the top two of the group maxima
     int wr[NS];             // the range where the best rose
+    // The loop runs one tile behind itself (Fp6Sched): what a block still owes when it ends (its last tile's
+    // last maxima, its second range's merge) is paid in the next block's first gaps, or in the drain.  The
+    // state starts at kLow, so the first block's payments change nothing: max(kLow, kLow), and a merge of
+    // kLow into (kLow, kLow) leaves w1, w2 and wr as they are (the compare is strict).
+    f32x4 acc[NS];
+    float half[NS], rm[2][NS];   // half: a tile's first maximum, waiting for its second
+    bool up[NS];
+    int rid_owed = 0;            // the range id of the merge in flight: carried, since the block has moved on
 #pragma unroll
-    for (int s = 0; s < NS; ++s) { w1[s] = kLow; w2[s] = kLow; wr[s] = 0; }
+    for (int s = 0; s < NS; ++s) {
+        w1[s] = kLow; w2[s] = kLow; wr[s] = 0;
+        acc[s] = f32x4{kLow, kLow, kLow, kLow};
+        half[s] = rm[0][s] = rm[1][s] = kLow;
+        up[s] = false;
+    }
+    auto merge_step = [&](int c, int step, float m, int rid) {
+        fp6_merge_step(step, m, rid, up[c], w1[c], w2[c], wr[c]);
+    };
 
     __syncthreads();
 
+    const uint8_t* bsrc = bdense;   // wave-uniform: the block being staged
+    const int32_t* ksrc = bhf;
     for (int blk = 0; blk < nblk; ++blk) {
         const int cur = blk & 1;
+        bsrc += TILE;
+        ksrc += kJB;
         if (blk + 1 < nblk)  // next block in flight under the MFMAs
-            S::dma(bdense + (size_t)(blk + 1) * TILE, bhf + (blk + 1) * kJB, lds + (cur ^ 1) * TILE,
-                   kbase + (cur ^ 1) * kJB, wave, lane);
+            S::dma(bsrc, ksrc, lds + (cur ^ 1) * TILE, kbase + (cur ^ 1) * kJB, wave, dl);
         const int8_t* tl = lds + cur * TILE;
         const float* kl = reinterpret_cast<const float*>(kbase + cur * kJB);
-        float rm[NS];
+        // the first k-step's operand and chain starts: behind the barrier that published the slot
+        Fp6Operand av;
+        av.lo = *reinterpret_cast<const i32x4*>(tl + lo_b[0]);
+        av.hi = lds_read_b64(tl + hi_b[0]);
+        // the lane's four candidate rows of a tile: h_j starts every chain
+        f32x4 hv = *reinterpret_cast<const f32x4*>(kl + 4 * grp);
 #pragma unroll
         for (int jt = 0; jt < JT; ++jt) {
-            if (jt % VG == 0) {
-#pragma unroll
-                for (int s = 0; s < NS; ++s) rm[s] = kLow;
-            }
-            // the lane's four candidate rows of this tile: h_j starts every chain
-            const f32x4 hv = *reinterpret_cast<const f32x4*>(kl + jt * MF + 4 * grp);
-            f32x4 acc[NS];
-#pragma unroll
-            for (int s = 0; s < NS; ++s) acc[s] = hv;
+            const int R = jt / VG, tt = jt % VG;   // the tile's range in the block, the tile in its range
+            f32x4 hv_n = hv;
 #pragma unroll
             for (int kk = 0; kk < KK; ++kk) {
-                Fp6Operand av;
-                av.lo = *reinterpret_cast<const i32x4*>(tl + lo_b[kk] + jt * MF * S::LB);
-                av.hi = lds_read_b64(tl + hi_b[kk] + jt * MF * S::HB);
-#pragma unroll
-                for (int s = 0; s < NS; ++s)
-                    acc[s] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av.tuple(), bq[s][kk].tuple(), acc[s], 2, 2,
-                                                                              0, kScale, 0, kScale);
-            }
-            // 2 VALU per 4 distances; the accumulators' first reader is plain C++ (match_kernel's note)
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                rm[s] = __builtin_fmaxf(__builtin_fmaxf(rm[s], acc[s][0]), acc[s][1]);
-                rm[s] = __builtin_fmaxf(__builtin_fmaxf(rm[s], acc[s][2]), acc[s][3]);
-            }
-            if (jt % VG == VG - 1) {
-                const int rid = blk * (JT / VG) + jt / VG;
+                Fp6Operand av_n = av;
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int s = 0; s < NS; ++s) {
-                    const bool up = rm[s] > w1[s];   // strict: the earliest range on ties; one compare serves both
-                    wr[s] = up ? rid : wr[s];
-                    w2[s] = __builtin_amdgcn_fmed3f(w1[s], w2[s], rm[s]);
-                    w1[s] = up ? rm[s] : w1[s];
+                    acc[s] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av.tuple(), bq[s][kk].tuple(),
+                                                                              kk == 0 ? hv : acc[s], 2, 2, 0, kScale, 0,
+                                                                              kScale);
+                    __builtin_amdgcn_sched_barrier(0);   // the source order is the issue order
+                    if (s == 0) {
+                        // Operand reads run one k-step ahead (none across the block's end: the slot is not
+                        // published).  They issue behind the k-step's first MFMA, not in front of it: the
+                        // compiler waits for this k-step's operand with lgkmcnt(0), which must not catch them.
+                        if (kk + 1 < KK) {
+                            av_n.lo = *reinterpret_cast<const i32x4*>(tl + lo_b[kk + 1] + jt * MF * S::LB);
+                            av_n.hi = lds_read_b64(tl + hi_b[kk + 1] + jt * MF * S::HB);
+                        } else if (jt + 1 < JT) {
+                            av_n.lo = *reinterpret_cast<const i32x4*>(tl + lo_b[0] + (jt + 1) * MF * S::LB);
+                            av_n.hi = lds_read_b64(tl + hi_b[0] + (jt + 1) * MF * S::HB);
+                            hv_n = *reinterpret_cast<const f32x4*>(kl + (jt + 1) * MF + 4 * grp);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    const int gp = kk * NS + s;
+                    // 2 VALU per 4 distances; the accumulators' first reader is plain C++ (match_kernel's note)
+                    if (const int c = SC::chain(gp, 0); c < NS) {
+                        // the tile these maxima belong to: this one or the one before.  A range's first tile
+                        // starts from kLow (a two-input max would cost a canonicalising v_max_f32 per value)
+                        const int of = tt - SC::back(gp, 0);
+                        const float from = of < 0 ? rm[R ^ 1][c] : of == 0 ? kLow : rm[R][c];
+                        half[c] = __builtin_fmaxf(__builtin_fmaxf(from, acc[c][0]), acc[c][1]);
+                    }
+                    if (const int c = SC::chain(gp, 1); c < NS)
+                        rm[tt == 0 && SC::back(gp, 1) ? R ^ 1 : R][c] =
+                            __builtin_fmaxf(__builtin_fmaxf(half[c], acc[c][2]), acc[c][3]);
+#pragma unroll
+                    for (int j = 0; j < SC::kBudget; ++j)
+                        if (const int k = SC::merge(tt * SC::MPT + gp, j); k >= 0) {
+                            __builtin_amdgcn_sched_barrier(0);   // every step in its place
+                            merge_step(SC::merge_chain(k), SC::merge_step(k), rm[R ^ 1][SC::merge_chain(k)], rid_owed);
+                        }
+                    __builtin_amdgcn_sched_barrier(0);
                 }
+                av = av_n;
             }
+            hv = hv_n;
+            if (tt == VG - 1) rid_owed = blk * (JT / VG) + R;   // this range's merge rides under the next range
         }
         __syncthreads();  // drains this wave's DMA; next block visible to all waves
     }
+    // drain: the last tile's owed maxima, then the last range's merge
+#pragma unroll
+    for (int s = SC::kOwedFirst; s < NS; ++s)
+        half[s] = __builtin_fmaxf(__builtin_fmaxf(rm[1][s], acc[s][0]), acc[s][1]);
+#pragma unroll
+    for (int s = SC::kOwedSecond; s < NS; ++s)
+        rm[1][s] = __builtin_fmaxf(__builtin_fmaxf(half[s], acc[s][2]), acc[s][3]);
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+#pragma unroll
+        for (int step = 0; step < 4; ++step) merge_step(s, step, rm[1][s], rid_owed);
 
     // value_only_tail decides 64 query rows (four tiles, one per lane group) per call
 #pragma unroll

@@ -17,10 +17,14 @@
 // integer g_a g_b), the form an FP6 certified filter would run.
 // Build: hipcc -O3 --offload-arch=gfx950 -o tools/mfma_mx_peak tools/mfma_mx_peak.hip
 // Run:   tools/mfma_mx_peak ITERS   (a multiple of 4)
+//        tools/mfma_mx_peak ITERS tile8   (a multiple of 8): only the two arms of kern_fp6_tile8
 #include <hip/hip_runtime.h>
 #include <climits>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+
+#include "../3d_reconstruction_amd/csrc/fp6_sched.h"
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
@@ -181,6 +185,174 @@ __global__ __launch_bounds__(256, 2) void kern_mx(const int* __restrict__ seed, 
     out[blockIdx.x * blockDim.x + threadIdx.x] = t1[0] + t2[0] + t1[1] + t2[1] + t1[2] + t2[2] + t1[3] + t2[3];
 }
 
+// The FP6 match kernel's real shape (match.hip, match_fp6_kernel<256>): 8 chains per wave, two k-steps per
+// tile, 6-register operands, the f32 group-max epilogue with the per-range merge every 4th tile, unit
+// scale, 2 waves per SIMD.  PIPE 0: the tile's 16 MFMAs, then its 16 max3, then (every 4th tile) the 32
+// merge instructions, in the order the compiler chooses (clustered).  PIPE 1: the same instructions in the
+// order of the kernel's own Fp6Sched<2, 8> (csrc/fp6_sched.h): chain s's two max3 in gaps 13 + s and 14 + s
+// of its tile (five MFMAs behind the chain's last, the last chains under the next tile's first MFMAs), the
+// merge of a finished range in the free slots of the next range's first two tiles, at most two VALU per
+// gap; every gap is closed by a scheduling barrier, so the source order is the issue order.
+typedef int i32x2 __attribute__((ext_vector_type(2)));
+struct Op6 {
+    i32x4 lo;
+    i32x2 hi;
+    __device__ i32x8 tuple() const { return i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], 0, 0}; }
+    __device__ void set(int e, int x) { if (e < 4) lo[e] = x; else hi[e - 4] = x; }
+};
+template <int PIPE>
+__global__ __launch_bounds__(256, 2) void kern_fp6_tile8(const int* __restrict__ seed, int iters, int* out) {
+    constexpr int NS = 8, KK = 2, VG = 4;
+    using SC = sfmhip::Fp6Sched<KK, NS>;
+    constexpr int kScale = (int)0x82828282;
+    const float kLow = -16777216.f;
+    const int lane = threadIdx.x & 63;
+    Op6 a[KK], b[NS][KK];   // 32 codes = 24 bytes in 6 registers, as the kernel holds them
+#pragma unroll
+    for (int k = 0; k < KK; ++k)
+#pragma unroll
+        for (int e = 0; e < 6; ++e) {
+            a[k].set(e, seed[(blockIdx.x * 97 + lane * 13 + k * 7 + e) & 4095]);
+#pragma unroll
+            for (int t = 0; t < NS; ++t) b[t][k].set(e, seed[(blockIdx.x * 31 + lane * 5 + k * 11 + e * 3 + t * 17) & 4095]);
+        }
+    f32x4 hv;
+    for (int e = 0; e < 4; ++e) hv[e] = (float)(seed[(lane * 3 + e) & 4095] >> 9);
+    float f1[NS], f2[NS], rm[2][NS], half[NS];
+    int wr[NS];
+    bool up[NS];
+    f32x4 acc[NS];
+#pragma unroll
+    for (int t = 0; t < NS; ++t) {
+        f1[t] = f2[t] = rm[0][t] = rm[1][t] = half[t] = kLow;
+        wr[t] = 0;
+        up[t] = false;
+        acc[t] = f32x4{kLow, kLow, kLow, kLow};
+    }
+#define MERGE_STEP(c, step, m, rid) sfmhip::fp6_merge_step(step, m, rid, up[c], f1[c], f2[c], wr[c])
+    int rid_owed = 0;
+    for (int it = 0; it < iters; it += 2 * VG) {   // one 128-candidate block: 8 tiles, two ranges
+#pragma unroll
+        for (int jt = 0; jt < 2 * VG; ++jt) {
+            const int R = jt / VG, tt = jt % VG;
+            asm volatile("" : "+v"(hv));
+            if (PIPE == 0) {
+#pragma unroll
+                for (int k = 0; k < KK; ++k)
+                    asm volatile("" : "+v"(a[k].lo), "+v"(a[k].hi));
+#pragma unroll
+                for (int t = 0; t < NS; ++t) acc[t] = hv;
+#pragma unroll
+                for (int k = 0; k < KK; ++k)
+#pragma unroll
+                    for (int t = 0; t < NS; ++t)
+                        acc[t] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[k].tuple(), b[t][k].tuple(), acc[t], 2, 2,
+                                                                                  0, kScale, 0, kScale);
+#pragma unroll
+                for (int t = 0; t < NS; ++t) {
+                    if (tt == 0) rm[0][t] = kLow;
+                    rm[0][t] = __builtin_fmaxf(__builtin_fmaxf(rm[0][t], acc[t][0]), acc[t][1]);
+                    rm[0][t] = __builtin_fmaxf(__builtin_fmaxf(rm[0][t], acc[t][2]), acc[t][3]);
+                }
+                if (tt == VG - 1) {
+                    const int rid = (it >> 2) + R;
+#pragma unroll
+                    for (int t = 0; t < NS; ++t)
+#pragma unroll
+                        for (int step = 0; step < 4; ++step) MERGE_STEP(t, step, rm[0][t], rid);
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < KK; ++k) {
+                    asm volatile("" : "+v"(a[k].lo), "+v"(a[k].hi));
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int t = 0; t < NS; ++t) {
+                        acc[t] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[k].tuple(), b[t][k].tuple(),
+                                                                                  k == 0 ? hv : acc[t], 2, 2, 0, kScale, 0,
+                                                                                  kScale);
+                        __builtin_amdgcn_sched_barrier(0);
+                        const int g = k * NS + t;
+                        if (const int c = SC::chain(g, 0); c < NS) {
+                            const int of = tt - SC::back(g, 0);   // the tile these maxima belong to
+                            const float from = of < 0 ? rm[R ^ 1][c] : of == 0 ? kLow : rm[R][c];
+                            half[c] = __builtin_fmaxf(__builtin_fmaxf(from, acc[c][0]), acc[c][1]);
+                        }
+                        if (const int c = SC::chain(g, 1); c < NS)
+                            rm[tt == 0 && SC::back(g, 1) ? R ^ 1 : R][c] =
+                                __builtin_fmaxf(__builtin_fmaxf(half[c], acc[c][2]), acc[c][3]);
+#pragma unroll
+                        for (int j = 0; j < SC::kBudget; ++j)
+                            if (const int m = SC::merge(tt * SC::MPT + g, j); m >= 0) {
+                                __builtin_amdgcn_sched_barrier(0);
+                                MERGE_STEP(SC::merge_chain(m), SC::merge_step(m), rm[R ^ 1][SC::merge_chain(m)], rid_owed);
+                            }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+                if (tt == VG - 1) rid_owed = (it >> 2) + R;
+            }
+        }
+    }
+    if (PIPE == 1) {   // drain: the last tile's owed maxima and the last range's merge
+#pragma unroll
+        for (int t = SC::kOwedFirst; t < NS; ++t) half[t] = __builtin_fmaxf(__builtin_fmaxf(rm[1][t], acc[t][0]), acc[t][1]);
+#pragma unroll
+        for (int t = SC::kOwedSecond; t < NS; ++t) rm[1][t] = __builtin_fmaxf(__builtin_fmaxf(half[t], acc[t][2]), acc[t][3]);
+#pragma unroll
+        for (int t = 0; t < NS; ++t)
+#pragma unroll
+            for (int step = 0; step < 4; ++step) MERGE_STEP(t, step, rm[1][t], rid_owed);
+    }
+    int r = 0;
+#pragma unroll
+    for (int t = 0; t < NS; ++t) r += (int)f1[t] + (int)f2[t] + wr[t];
+#undef MERGE_STEP
+    out[blockIdx.x * blockDim.x + threadIdx.x] = r;   // the same value in both arms
+}
+
+// the two arms of the real shape, interleaved, REPS times each: per-arm min / median / max and the checksum
+static int run_tile8(const int* seed, int* out, int blocks, int iters) {
+    const int REPS = 7;
+    float ms[2][REPS];
+    long long sum[2] = {0, 0};
+    hipEvent_t e0, e1;
+    hipEventCreate(&e0);
+    hipEventCreate(&e1);
+    int* host = (int*)malloc((size_t)blocks * 256 * 4);
+    for (int rep = -1; rep < REPS; ++rep)   // rep -1 warms up
+        for (int arm = 0; arm < 2; ++arm) {
+            hipEventRecord(e0);
+            if (arm == 0) hipLaunchKernelGGL(kern_fp6_tile8<0>, dim3(blocks), dim3(256), 0, 0, seed, iters, out);
+            else hipLaunchKernelGGL(kern_fp6_tile8<1>, dim3(blocks), dim3(256), 0, 0, seed, iters, out);
+            hipEventRecord(e1);
+            if (hipEventSynchronize(e1) != hipSuccess) { printf("launch failed\n"); return 1; }
+            if (rep < 0) {
+                hipMemcpy(host, out, (size_t)blocks * 256 * 4, hipMemcpyDeviceToHost);
+                for (size_t i = 0; i < (size_t)blocks * 256; ++i) sum[arm] += host[i];
+            } else {
+                hipEventElapsedTime(&ms[arm][rep], e0, e1);
+            }
+        }
+    free(host);
+    // per wave: iters tiles x 8 chains x 16 x 16 outputs x d = 256 x 2 ops; 16 MFMAs per tile
+    const double ops = (double)blocks * 4 * iters * 8.0 * 16 * 16 * 256 * 2;
+    const double mfma_per_simd = (double)blocks * 4 * iters * 16 / (256.0 * 4);
+    const char* names[2] = {"clustered (compiler order)", "pipelined (Fp6Sched order)"};
+    for (int arm = 0; arm < 2; ++arm) {
+        float* m = ms[arm];
+        for (int i = 0; i < REPS; ++i)
+            for (int j = i + 1; j < REPS; ++j)
+                if (m[j] < m[i]) { float t = m[i]; m[i] = m[j]; m[j] = t; }
+        printf("fp6 8 chains x 2 k-steps, %-27s: min %.3f  median %.3f  max %.3f ms  %6.0f TOPS at the median, "
+               "%.1f ns per MFMA per SIMD, checksum %lld\n",
+               names[arm], m[0], m[REPS / 2], m[REPS - 1], ops / m[REPS / 2] / 1e9, m[REPS / 2] * 1e6 / mfma_per_simd,
+               sum[arm]);
+    }
+    printf("checksums %s\n", sum[0] == sum[1] ? "equal" : "DIFFER");
+    return sum[0] == sum[1] ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
     const int blocks = 256 * 2 * 8, iters = (argc > 1 ? atoi(argv[1]) : 2000) & ~3;
     int *seed, *out;
@@ -193,6 +365,7 @@ int main(int argc, char** argv) {
         h[i] = (int)x;   // uniform random bits: random int8 values, random fp6 / fp4 codes (no NaN encodings)
     }
     hipMemcpy(seed, h, sizeof(h), hipMemcpyHostToDevice);
+    if (argc > 2 && !strcmp(argv[2], "tile8")) return run_tile8(seed, out, blocks, iters & ~7);
     // per wave-iteration: 4 tiles x 16 x 16 outputs x d = 256 x 2 ops
     const double ops_iter = 4.0 * 16 * 16 * 256 * 2;
     const char* names[8] = {"int8 16x16x64 (today)", "int8 16x16x64 (today)", "fp6 e2m3 16x16x128 scaled",
