@@ -7,7 +7,8 @@ number-theoretic rather than bit-for-bit against the oracle:
 * pnp.hip `epnp_eig4_tri`: the four smallest eigenpairs of the Householder tridiagonal by
   Sturm-count trisection (leading-minor recurrence on the power-of-two-scaled
   matrix) and inverse iteration with partial pivoting (the four vectors in lockstep, modified
-  Gram-Schmidt after every step), restated step for step in numpy and checked against LAPACK
+  Gram-Schmidt after every step), restated step for step in numpy (tests/pnp_ref.py, which also
+  runs the oracle on it) and checked against LAPACK
   (numpy.linalg.eigh) on EPnP-like M^T M matrices.
 * geom_dev.h `cv_rng_sample_wave`: cv::RNG jump-ahead; the wave-parallel sampler gives the serial
   cv_rng_sample5 sequence and final state exactly.
@@ -15,6 +16,9 @@ number-theoretic rather than bit-for-bit against the oracle:
 import math
 
 import numpy as np
+
+from pnp_ref import eig4_tri as _eig4_tri
+from pnp_ref import householder_tridiag as _householder_tridiag
 
 
 def _butterfly(vals):
@@ -61,103 +65,6 @@ def test_reduce_scatter_matches_butterfly_bits():
         assert sorted(got) == list(range(K))
         for k in range(K):
             assert got[k] == ref[k], (K, k)   # identical floating-point sums
-
-
-def _householder_tridiag(A):
-    """EISPACK tred2-like reduction (the device order: column k reflected into rows k+1..)."""
-    A = A.copy()
-    n = A.shape[0]
-    Q = np.eye(n)
-    for k in range(n - 2):
-        x = A[k + 1:, k].copy()
-        n2 = x @ x
-        x0 = x[0]
-        s2 = n2 - x0 * x0
-        if not (s2 > 1e-300 * n2) or not (n2 > 0):
-            continue
-        alpha = -math.sqrt(n2) if x0 >= 0 else math.sqrt(n2)
-        v = x.copy()
-        v[0] = x0 - alpha
-        beta = 2.0 / (v @ v)
-        H = np.eye(n)
-        H[k + 1:, k + 1:] -= beta * np.outer(v, v)
-        A = H @ A @ H
-        Q = Q @ H
-    return np.diag(A).copy(), np.diag(A, 1).copy(), Q
-
-
-def _eig4_tri(d, e):
-    """pnp.hip epnp_eig4_tri restated: 4 smallest eigenpairs of tridiag(d, e)."""
-    n = len(d)
-    r = np.abs(np.concatenate([[0.0], e])) + np.abs(np.concatenate([e, [0.0]]))
-    lo, hi = np.min(d - r), np.max(d + r)
-    tn = np.max(np.abs(d) + r)
-    sc = math.ldexp(1.0, -(math.frexp(tn)[1] - 1) - 1) if tn > 0 else 1.0
-    ds, es2 = d * sc, (e * sc) ** 2
-
-    def count(x):
-        p0, p1 = 1.0, ds[0] - x
-        c = int(p1 < 0)
-        for i in range(1, n):
-            p2 = (ds[i] - x) * p1 - es2[i - 1] * p0
-            c += int((p2 < 0) != (p1 < 0))
-            p0, p1 = p1, p2
-        return c
-
-    lams = []
-    for k in range(4):
-        a, b = lo * sc - 2.0 ** -50, hi * sc + 2.0 ** -50
-        for _ in range(30):
-            w = (b - a) / 3.0
-            m1, m2 = a + w, a + 2.0 * w
-            if count(m1) > k:
-                b = m1
-            elif count(m2) > k:
-                a, b = m1, m2
-            else:
-                a = m2
-        lams.append(0.5 * (a + b) / sc)
-    tol = 2.0 ** -52 * max(tn, 2.0 ** -1000)
-    facts, ys = [], []
-    for k in range(4):
-        lk = lams[k]
-        u0, u1, u2, lm, sw = np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(n - 1), np.zeros(n - 1, bool)
-        pd, p1, p2 = d[0] - lk, e[0], 0.0
-        for i in range(n - 1):
-            nd, n1, n2 = e[i], d[i + 1] - lk, (e[i + 1] if i + 1 < n - 1 else 0.0)
-            sw[i] = abs(nd) > abs(pd)
-            if not sw[i]:
-                piv = (-tol if pd < 0 else tol) if abs(pd) < tol else pd
-                m = nd / piv
-                u0[i], u1[i], u2[i], lm[i] = piv, p1, p2, m
-                pd, p1, p2 = n1 - m * p1, n2 - m * p2, 0.0
-            else:
-                m = pd / nd
-                u0[i], u1[i], u2[i], lm[i] = nd, n1, n2, m
-                pd, p1, p2 = p1 - m * n1, p2 - m * n2, 0.0
-        u0[n - 1] = (-tol if pd < 0 else tol) if abs(pd) < tol else pd
-        facts.append((u0, u1, u2, lm, sw))
-        ys.append(np.array([1.0 / (1.0 + ((i * 7 + k * 5) % 12)) for i in range(n)]))
-    # the four iterations in lockstep (one lane each); every step ends with modified
-    # Gram-Schmidt in order 0..3 against the other lanes' current iterates
-    for _ in range(3):
-        for k in range(4):
-            u0, u1, u2, lm, sw = facts[k]
-            y = ys[k]
-            for i in range(n - 1):
-                if sw[i]:
-                    y[i], y[i + 1] = y[i + 1], y[i]
-                y[i + 1] -= lm[i] * y[i]
-            y[n - 1] /= u0[n - 1]
-            y[n - 2] = (y[n - 2] - u1[n - 2] * y[n - 1]) / u0[n - 2]
-            for i in range(n - 3, -1, -1):
-                y[i] = (y[i] - u1[i] * y[i + 1] - u2[i] * y[i + 2]) / u0[i]
-        for j in range(4):
-            ys[j] = ys[j] / math.sqrt(ys[j] @ ys[j])
-            for k in range(j + 1, 4):
-                ys[k] = ys[k] - (ys[k] @ ys[j]) * ys[j]
-    Y = ys
-    return np.array(lams), np.array(Y).T
 
 
 def _epnp_mtm(rng, f=1500.0):

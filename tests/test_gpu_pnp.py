@@ -76,3 +76,113 @@ def test_pnp_five_points_and_batch(sfm, gpu):
     with pytest.raises(NotImplementedError):
         sfm.solvePnPRansac(X[:4], uv[:4], K)
 
+
+
+# ---------------------------------------------------------------------------------------------
+# Past the first chunk, the centred camera and the staged LM: the scenes of tests/pnp_ref.py.
+# Every scene there is admissible (tests/test_pnp_scenes_cpu.py): the oracle's outcome does not
+# depend on the eigen-solver's choice inside EPnP's null pair, so any disagreement is the kernel's.
+import pnp_ref as pr   # noqa: E402
+
+_CV2_NAMES = dict(iterations="iterationsCount", reprojection_error="reprojectionError", confidence="confidence")
+_F32_FORM = ("off-centre", "two-adoptions-partial-last-chunk")     # imagePoints (n, 1, 2) float32
+
+
+def _launch(sfm, problems, cams, **params):
+    """One sfmhip_pnp_ransac launch over [(X, uv), ...] -> numpy outputs and the offsets."""
+    import torch
+    offs = np.cumsum([0] + [len(p[0]) for p in problems])
+    X = np.concatenate([np.asarray(p[0], np.float64).reshape(-1, 3) for p in problems])
+    uv = np.concatenate([np.asarray(p[1], np.float64).reshape(-1, 2) for p in problems])
+    res = sfm.verify.pnp_ransac_batched(X, uv, torch.tensor(offs), cams, **params)
+    return {k: t.cpu().numpy() for k, t in res.items()}, offs
+
+
+@pytest.mark.parametrize("name", pr.SCENE_NAMES)
+def test_pnp_scene_matches_oracle(sfm, gpu, name):
+    X, uv, K = pr.get_scene(name)[:3]
+    n, params = len(X), pr.params_of(name)
+    adopted, (oko, ro, to, idxo), iters = pr.oracle_trace(name)
+    g, _ = _launch(sfm, [(X, uv)], sfm.verify._cam(K), **params)
+    mask = g["mask"]
+    print(f"{name}: n {n} ok {int(g['ok'][0])}/{int(oko)} iters {int(g['iters'][0])}/{iters} "
+          f"inliers {int(g['n_inliers'][0])}/{0 if not oko else len(idxo)} oracle adoptions {adopted}")
+    assert int(g["ok"][0]) == int(oko)
+    assert int(g["iters"][0]) == iters
+    assert int(g["n_inliers"][0]) == int(mask.sum())
+    if not oko:
+        assert int(g["n_inliers"][0]) == 0 and not mask.any()
+    else:
+        want = np.zeros(n, np.uint8)
+        want[idxo.ravel()] = 1
+        print(f"{name}: max |gpu - oracle| rvec {np.abs(g['rvec'][0] - ro.ravel()).max():.3e} "
+              f"tvec {np.abs(g['tvec'][0] - to.ravel()).max():.3e}")
+        assert np.array_equal(mask, want)
+        np.testing.assert_allclose(g["rvec"][0], ro.ravel(), rtol=0, atol=1e-7)
+        np.testing.assert_allclose(g["tvec"][0], to.ravel(), rtol=0, atol=1e-7)
+    # the cv2 call form gives the same results
+    kw = {_CV2_NAMES[k]: v for k, v in params.items()}
+    ip = uv.reshape(n, 1, 2).astype(np.float32) if name in _F32_FORM else np.array(uv)
+    ok, r, tt, idx = sfm.solvePnPRansac(np.array(X), ip, np.array(K), np.zeros((5, 1)), **kw)
+    assert ok == oko
+    if ok:
+        assert idx.dtype == np.int32 and np.array_equal(idx, idxo)
+        assert r.shape == (3, 1) and tt.shape == (3, 1)
+        assert np.array_equal(r.ravel(), g["rvec"][0]) and np.array_equal(tt.ravel(), g["tvec"][0])
+    else:
+        assert r is None and tt is None and idx is None
+
+
+def test_pnp_ragged_batch_equals_singles(sfm, gpu):
+    import torch
+    cam = sfm.verify._cam
+    five_a = pr.scene(5, 11, outlier=0.0, noise=0.0, K=pr.KC)
+    five_b = pr.scene(5, 12, outlier=0.0, noise=0.0, K=pr.K3)
+    probs = [(np.zeros((0, 3)), np.zeros((0, 2)), pr.KC),
+             (five_b[0][:3], five_b[1][:3], pr.K3), five_a, pr.get_scene("off-centre"), five_b, pr.get_scene("no-model"),
+             pr.get_scene("two-chunks"), pr.scene(n=7000, seed=6, K=pr.K3), pr.scene(n=6, seed=8, outlier=0.0, K=pr.KC)]
+    assert [len(p[0]) for p in probs] == [0, 3, 5, 400, 5, 200, 513, 7000, 6]
+    cams = torch.tensor(np.stack([cam(p[2]) for p in probs]))               # (P, 4): a row per problem
+    assert len({tuple(c) for c in cams.tolist()}) == 3
+    b, offs = _launch(sfm, probs, cams)
+    b2, _ = _launch(sfm, probs, cams)
+    okb = b["ok"].astype(bool)
+    assert okb.tolist() == [False, False, True, True, True, False, True, True, True]
+    for k in ("ok", "n_inliers", "iters", "mask"):
+        assert np.array_equal(b[k], b2[k]), k                               # launch to launch
+    for k in ("rvec", "tvec"):
+        assert np.array_equal(b[k][okb], b2[k][okb]), k
+    for i, p in enumerate(probs):
+        sl = slice(offs[i], offs[i + 1])
+        if len(p[0]) < 5:
+            assert (b["ok"][i], b["iters"][i], b["n_inliers"][i]) == (0, 0, 0) and not b["mask"][sl].any()
+        if len(p[0]) == 0:
+            continue                                                         # no single launch of nothing
+        s, _ = _launch(sfm, [p], cams[i:i + 1])
+        for k in ("ok", "n_inliers", "iters"):
+            assert b[k][i] == s[k][0], (i, k)
+        assert np.array_equal(b["mask"][sl], s["mask"]), i
+        if okb[i]:
+            assert np.array_equal(b["rvec"][i], s["rvec"][0]) and np.array_equal(b["tvec"][i], s["tvec"][0]), i
+        if len(p[0]) == 5:
+            assert b["mask"][sl].tolist() == [1] * 5 and b["iters"][i] == 1 and b["n_inliers"][i] == 5
+    assert b["iters"][5] == 100 and b["n_inliers"][5] == 0 and not b["mask"][offs[5]:offs[6]].any()
+
+
+def test_pnp_five_point_sweep(sfm, gpu):
+    """Raw EPnP (n == 5: no RANSAC, no refinement) on 256 poses with rotations of about 1 rad."""
+    poses, spread = pr.sweep_reference()
+    probs = [pr.sweep_scene(s) for s in range(pr.SWEEP)]
+    g, _ = _launch(sfm, probs, sfm.verify._cam(pr.KO))
+    assert np.all(g["ok"] == 1) and np.all(g["iters"] == 1) and np.all(g["n_inliers"] == 5) and np.all(g["mask"] == 1)
+    take = spread <= pr.SWEEP_SPREAD
+    assert int((~take).sum()) <= pr.SWEEP_MAX_EXCLUDED
+    got = np.concatenate([g["rvec"], g["tvec"]], 1)
+    dev = np.abs(got - poses).max(1)
+    truth = np.array([max(np.abs(og.rodrigues(got[s, :3]) - og.rodrigues(probs[s][3])).max(),
+                          np.abs(got[s, 3:] - probs[s][4]).max()) for s in range(pr.SWEEP)])
+    print(f"5-point sweep: {int((~take).sum())} of {pr.SWEEP} left out (variant spread > {pr.SWEEP_SPREAD:g}); "
+          f"of the rest: max |gpu - oracle| {dev[take].max():.3e}, max |gpu - truth| {truth[take].max():.3e}; "
+          f"of those left out: max |gpu - oracle| {dev[~take].max() if (~take).any() else 0.0:.3e}")
+    assert dev[take].max() <= 1e-7
+    assert truth[take].max() <= 1e-5
