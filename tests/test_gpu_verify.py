@@ -121,7 +121,7 @@ def test_essential_inliers_is_matching_py_count(sfm, gpu, scene):
         assert got[p] == ngo, p
 
 
-def _ess_run(sfm, pts0, pts1, K, max_iters=1000, prob=0.999, **env):
+def _ess_run(sfm, pts0, pts1, K, max_iters=1000, prob=0.999, threshold=1.0, **env):
     import os
     keys = ("SFMHIP_ESS_MONO", "SFMHIP_ESS_RECE")
     old = {k: os.environ.pop(k, None) for k in keys}
@@ -131,7 +131,7 @@ def _ess_run(sfm, pts0, pts1, K, max_iters=1000, prob=0.999, **env):
         sfm.knobs_reload()
         v = sfm.verify
         a, b, of = v.pack_pairs(pts0, pts1)
-        r = v.find_essential_batched(a, b, of, v._cam(K), prob=prob, max_iters=max_iters)
+        r = v.find_essential_batched(a, b, of, v._cam(K), prob=prob, threshold=threshold, max_iters=max_iters)
         torch.cuda.synchronize()
         return {k: t.cpu().numpy() for k, t in r.items()}
     finally:
@@ -185,3 +185,171 @@ def test_balanced_bench_scene_matches_monolithic(sfm, gpu):
             assert np.array_equal(bal[k], mono[k]), (env, k)
     assert mono["iters"].max() > 64 and mono["iters"].min() >= 1   # round 1 exercised
 
+
+
+# ---------------------------------------------------------------------------------------------
+# Beyond the centred square camera: the scenes of tests/ess_ref.py.  Every scene there is admissible
+# (tests/test_ess_scenes_cpu.py): the oracle's outcome does not depend on a 1e-8 change of the
+# candidate models or on the order of a sample's models, and recoverPose's winner is strict with no
+# cheirality test near its boundary, so any disagreement is the kernel's.
+import ess_ref as er   # noqa: E402
+
+
+def _sign_dev(a, b):
+    return float(min(np.abs(a - b).max(), np.abs(a + b).max()))
+
+
+def _fe_launch(sfm, names, cams=None, **params):
+    """One sfmhip_find_essential launch over the named scenes -> numpy outputs and the offsets."""
+    v = sfm.verify
+    scs = [er.fe_scene(n) for n in names]
+    a, b, of = v.pack_pairs([s["pts0"] for s in scs], [s["pts1"] for s in scs])
+    if cams is None:
+        cams = np.stack([v._cam(s["K"]) for s in scs])
+    r = v.find_essential_batched(a, b, of, cams, **params)
+    return {k: t.cpu().numpy() for k, t in r.items()}, of.cpu().numpy()
+
+
+def _fe_same(x, y, i, j, ox, oy):
+    """Pair i of launch x and pair j of launch y carry the same bits."""
+    for k in ("n_models", "n_inliers", "iters"):
+        assert x[k][i] == y[k][j], k
+    assert np.array_equal(x["mask"][ox[i]:ox[i + 1]], y["mask"][oy[j]:oy[j + 1]])
+    nm = x["n_models"][i]
+    assert np.array_equal(x["E"][i, :nm], y["E"][j, :nm])
+
+
+@pytest.mark.parametrize("name", er.FE_NAMES)
+def test_fe_scene_matches_oracle(sfm, gpu, name):
+    sc, params, tr = er.fe_scene(name), er.fe_params(name), er.fe_trace(name)
+    n = len(sc["pts0"])
+    g, _ = _fe_launch(sfm, [name], **params)
+    print(f"{name}: n {n} models {g['n_models'][0]} iters {g['iters'][0]}/{tr['iters']} "
+          f"inliers {g['n_inliers'][0]}/{int(tr['mask'].sum())} oracle adoptions {tr['adoptions']}")
+    assert g["n_models"][0] == 1
+    assert g["iters"][0] == tr["iters"]
+    assert g["n_inliers"][0] == int(tr["mask"].sum()) == int(g["mask"].sum())
+    assert np.array_equal(g["mask"], tr["mask"].ravel())
+    Eg = g["E"][0, 0].reshape(3, 3)
+    print(f"{name}: max |E gpu -+ E oracle| {_sign_dev(Eg, tr['E']):.3e}")
+    assert _same_up_to_sign(Eg, tr["E"], E_TOL), (Eg, tr["E"])
+    # the cv2 call form: the same results
+    E, mask = sfm.verify.findEssentialMat(sc["pts0"], sc["pts1"], sc["K"], sfm.verify.RANSAC,
+                                          params.get("prob", 0.999), params.get("threshold", 1.0),
+                                          params.get("max_iters", 1000))
+    assert E.shape == (3, 3) and mask.shape == (n, 1) and mask.dtype == np.uint8
+    assert np.array_equal(mask, tr["mask"]) and np.array_equal(E, Eg)
+
+
+@pytest.mark.parametrize("name", er.FE_NAMES)
+def test_fe_scene_balanced_equals_monolithic(sfm, gpu, name):
+    sc, p = er.fe_scene(name), er.fe_params(name)
+    args = ([sc["pts0"]], [sc["pts1"]], sc["K"], p.get("max_iters", 1000), p.get("prob", 0.999), p.get("threshold", 1.0))
+    mono = _ess_run(sfm, *args, MONO=1)
+    assert mono["n_models"][0] == 1 and mono["iters"][0] == er.fe_trace(name)["iters"]
+    for env in ({}, {"RECE": 0}):
+        bal = _ess_run(sfm, *args, **env)
+        for k in ("E", "n_models", "n_inliers", "iters", "mask"):
+            assert np.array_equal(bal[k], mono[k]), (env, k)
+
+
+def test_fe_ragged_batch_with_a_camera_per_pair(sfm, gpu):
+    names = er.FE_DEFAULT
+    cams = np.stack([sfm.verify._cam(er.fe_scene(n)["K"]) for n in names])
+    assert cams.shape == (len(names), 4) and len({tuple(c) for c in cams}) >= 4
+    b, ob = _fe_launch(sfm, names, cams)
+    b2, _ = _fe_launch(sfm, names, cams)
+    bd, _ = _fe_launch(sfm, names, torch.tensor(cams, device=gpu))
+    for i, name in enumerate(names):
+        s, os_ = _fe_launch(sfm, [name])
+        _fe_same(b, s, i, 0, ob, os_)
+        _fe_same(b, b2, i, i, ob, ob)
+        _fe_same(b, bd, i, i, ob, ob)
+        assert b["iters"][i] == er.fe_trace(name)["iters"]
+        assert np.array_equal(b["mask"][ob[i]:ob[i + 1]], er.fe_trace(name)["mask"].ravel())
+    # one row is broadcast; any other row count is refused
+    same = [n for n in names if tuple(sfm.verify._cam(er.fe_scene(n)["K"])) == er.CAM_OFF]
+    assert len(same) >= 3
+    rows, orows = _fe_launch(sfm, same)
+    row = np.array([er.CAM_OFF])
+    for one in (row, torch.tensor(row, device=gpu)):
+        got, _ = _fe_launch(sfm, same, one)
+        for i in range(len(same)):
+            _fe_same(got, rows, i, i, orows, orows)
+    two = np.array([er.CAM_OFF, er.CAM_B])
+    for bad in (two, torch.tensor(two, device=gpu), torch.tensor(two)):
+        with pytest.raises(ValueError):
+            _fe_launch(sfm, same, bad)
+
+
+def _rp_check(got, d, n_keep=None):
+    """(n_good, R, t, mask) of the device against recover_pose_detail -> the largest R and t deviations."""
+    ng, R, t, m = got
+    k = d["k"]
+    want = d["masks"][k] if n_keep is None else d["masks"][k][n_keep]
+    assert ng == d["counts"][k] == int((m > 0).sum())
+    assert m.dtype == np.uint8 and set(np.unique(m)) <= {0, 255}
+    assert np.array_equal(m.ravel() > 0, want)
+    Ro, to = d["cands"][k]
+    np.testing.assert_allclose(R, Ro, rtol=0, atol=1e-8)
+    np.testing.assert_allclose(t, to, rtol=0, atol=1e-8)
+    return float(np.abs(R - Ro).max()), float(np.abs(t - to).max())
+
+
+@pytest.mark.parametrize("name", er.RP_NAMES)
+def test_rp_scene_matches_oracle(sfm, gpu, name):
+    E, a, b, K, dist, mask, _ = er.rp_scene(name)
+    E = np.array(E)             # the shared scene is read-only; the call gets its own copy
+    v = sfm.verify
+    d, dm = er.rp_detail(name), er.rp_detail(name, masked=True)
+    dev = [_rp_check(v.recoverPose(E, a, b, K, distanceThresh=dist), d)]
+    keep = mask > 0
+    full = v.recoverPose(E, a, b, K, mask=mask.reshape(-1, 1), distanceThresh=dist)       # the mask= form
+    dev.append(_rp_check(full, dm))
+    assert not full[3][~keep].any()
+    comp = v.recoverPose(E, a[keep], b[keep], K, distanceThresh=dist)                      # the compacted call
+    dev.append(_rp_check(comp, dm, keep))
+    assert np.array_equal(comp[1], full[1]) and np.array_equal(comp[2], full[2])
+    print(f"{name}: n {len(a)} dist {dist} counts {d['counts']} masked {dm['counts']} oracle k {d['k']}; "
+          f"max |R gpu - R oracle| {max(x[0] for x in dev):.3e} max |t gpu - t oracle| {max(x[1] for x in dev):.3e}")
+
+
+def test_rp_batched_equals_singles(sfm, gpu):
+    """recover_pose_batched with a camera row per pair, with and without an input mask: the bits of
+    the single calls.  Two find-essential scenes join the first batch with the oracle's E, so that
+    the rows differ."""
+    v = sfm.verify
+    groups = {}
+    for name in er.RP_NAMES:
+        E, a, b, K, dist, mask, _ = er.rp_scene(name)
+        groups.setdefault(dist, []).append((np.array(E), a, b, K, mask))
+    for name in ("off-centre", "n-2049"):
+        sc, tr = er.fe_scene(name), er.fe_trace(name)
+        groups[50.0].append((tr["E"], sc["pts0"], sc["pts1"], sc["K"], tr["mask"].ravel()))
+    assert sorted(groups) == [8.0, 20.0, 50.0]
+    for dist, probs in groups.items():
+        a, b, of = v.pack_pairs([p[1] for p in probs], [p[2] for p in probs])
+        Es = np.stack([p[0].ravel() for p in probs])
+        cams = np.stack([v._cam(p[3]) for p in probs])
+        offs = of.cpu().numpy()
+        for masked in (False, True):
+            mk = np.concatenate([p[4] for p in probs]).astype(np.uint8) if masked else None
+            r = {k: t.cpu().numpy() for k, t in v.recover_pose_batched(Es, a, b, of, cams, mk, dist).items()}
+            for i, p in enumerate(probs):
+                ng, R, t, m = v.recoverPose(p[0], p[1], p[2], p[3], mask=p[4] if masked else None, distanceThresh=dist)
+                assert r["n_good"][i] == ng, (dist, masked, i)
+                assert np.array_equal(r["R"][i], R) and np.array_equal(r["t"][i], t.ravel())
+                assert np.array_equal(r["mask"][offs[i]:offs[i + 1]], m.ravel())
+    assert len({tuple(v._cam(p[3])) for p in groups[50.0]}) == 3
+
+
+def test_rp_all_zero_mask_is_a_tie(sfm, gpu):
+    """Nothing may be counted, so all four candidates tie at 0 and which one is returned is the
+    decomposition's choice: asserted as properties, not as parity."""
+    E, a, b, K, dist, mask, _ = er.rp_scene("n-769")
+    ng, R, t, m = sfm.verify.recoverPose(np.array(E), a, b, K, mask=np.zeros((len(a), 1), np.uint8), distanceThresh=dist)
+    assert ng == 0 and m.shape == (len(a), 1) and not m.any()
+    assert np.abs(R @ R.T - np.eye(3)).max() < 1e-12 and abs(np.linalg.det(R) - 1) < 1e-12
+    assert abs(np.linalg.norm(t) - 1) < 1e-12
+    cands = er.rp_detail("n-769")["cands"]
+    assert min(max(np.abs(R - Rc).max(), np.abs(t - tc).max()) for Rc, tc in cands) <= 1e-8
