@@ -16,6 +16,7 @@ import pytest
 import torch
 from scipy.optimize import least_squares
 
+import geom_ref as gr
 from oracle import ba as oba
 from oracle import geometry as og
 
@@ -202,6 +203,118 @@ def test_unchanged_sfm_py_least_squares_through_sfmhip(sfm, gpu):
     got = least_squares(_sfm_py_residual(cv2), x0, jac_sparsity=A, x_scale="jac", ftol=1e-8, args=(Ks[0], ps[0]))
     ref = least_squares(og.reprojection_error, x0, jac_sparsity=og.ba_sparse(500, len(x0), 6), x_scale="jac",
                         ftol=1e-8, args=(Ks[0], ps[0]))
+    assert got.success and ref.success
+    assert abs(got.nfev - ref.nfev) <= 1
+    assert np.abs(got.x - ref.x).max() <= 1e-6 * np.abs(ref.x).max()
+    assert abs(got.cost - ref.cost) <= 1e-6 * ref.cost + 1e-12
+
+
+# ---------------------------------------------------------------------------------------------
+# off the centred camera: a camera row per pair, admissible scenes only (tests/geom_ref.py)
+def _solve_batch(sfm, gpu, b, **kw):
+    scs = b["scenes"]
+    return _solve_gpu(sfm, gpu, [s["cam"] for s in scs], [s["K"] for s in scs], [s["X"] for s in scs],
+                      [s["pts"] for s in scs], **kw)
+
+
+def test_ba_solve_batched_per_pair_cameras_vs_oracle(sfm, gpu):
+    """One ragged batch, pairs of 1, 2, 3, 5, 0, 37, 300, 768 and 769 observations (fewer residuals
+    than camera parameters up to one more than the LDS holds), every pair with its own K row
+    (cameras A, B, C jittered), near and far starts, scene scale 1 and 2.5; each scene admissible
+    (test_geom_scenes_cpu.py).  The assertions of test_ba_solve_batched_vs_oracle, with the status
+    compared for equality."""
+    b = gr.ba_batch()
+    cam, X, res, off = _solve_batch(sfm, gpu, b)
+    for p, adm in enumerate(gr.ba_batch_oracle()):
+        if adm is None:
+            assert res["nfev"][p] == 0 and res["status"][p] == 1
+            continue
+        o, xo = adm[1]["oracle"], adm[1]["x"]
+        xg = np.concatenate([cam[p], X[off[p]:off[p + 1]].ravel()])
+        print(f"pair {p} n {off[p + 1] - off[p]}: gpu (nfev, njev, status) {(res['nfev'][p], res['njev'][p], res['status'][p])} "
+              f"oracle {(o['nfev'], o['njev'], o['status'])} |dx| / max |x| {np.abs(xg - xo).max() / np.abs(xo).max():.3e} "
+              f"cost {res['cost'][p]:.3e} oracle {o['cost']:.3e}")
+    for p, adm in enumerate(gr.ba_batch_oracle()):
+        if adm is None:
+            continue
+        o, xo = adm[1]["oracle"], adm[1]["x"]
+        assert (res["nfev"][p], res["njev"][p]) == (o["nfev"], o["njev"]), p
+        assert res["status"][p] == o["status"], p
+        xg = np.concatenate([cam[p], X[off[p]:off[p + 1]].ravel()])
+        assert np.abs(xg - xo).max() <= 1e-6 * np.abs(xo).max(), p
+        assert abs(res["cost"][p] - o["cost"]) <= 1e-6 * o["cost"] + 1e-12, p
+
+
+@pytest.mark.parametrize("ab", [7, 9])
+def test_ba_per_pair_cameras_forms_bit_identical(sfm, gpu, knob, ab):
+    """The same batch with all records in scratch (SFMHIP_AB=7) and in the fused form (SFMHIP_AB=9):
+    the bits of the default."""
+    b = gr.ba_batch()
+    out = []
+    for v in (0, ab):
+        knob("AB", v)
+        out.append(_solve_batch(sfm, gpu, b))
+    (c0, x0, r0, _), (c1, x1, r1, _) = out
+    assert np.array_equal(c0, c1) and np.array_equal(x0, x1)
+    for key in ("cost", "nfev", "njev", "status"):
+        assert np.array_equal(r0[key], r1[key]), key
+
+
+@pytest.mark.parametrize("kind", ["A", "B", "C"])
+def test_ba_stopping_table(sfm, gpu, kind):
+    """One admissible 300-point far scene per camera, stopped everywhere but at convergence:
+    max_nfev = 1, 2, 3 (status 0, nfev = njev = max_nfev), a gtol above the first |g| (status 1 at
+    nfev = 1, X and cam untouched bit for bit) and xtol = 1e-3 (status 3).  After the single step of
+    max_nfev = 2, x meets the oracle's at geom_ref.single_step_tol, 10x what Jacobian noise of
+    one FD quantum does to the oracle's own step."""
+    sc = gr.stop_scene(kind)
+    for name in gr.STOPS:
+        ok, info = gr.stop_oracle(kind, name)
+        o, xo = info["oracle"], info["x"]
+        cam, X, res, _ = _solve_gpu(sfm, gpu, [sc["cam"]], [sc["K"]], [sc["X"]], [sc["pts"]], **gr.stop_args(sc, name))
+        xg = np.concatenate([cam[0], X.ravel()])
+        dx = np.abs(xg - xo).max() / np.abs(xo).max()
+        print(f"camera {kind} {name}: gpu {(res['nfev'][0], res['njev'][0], res['status'][0])} oracle "
+              f"{(o['nfev'], o['njev'], o['status'])} |dx| / max |x| {dx:.3e}")
+        status, nfev = gr.STOP_EXPECT[name]
+        assert res["status"][0] == status == o["status"], name
+        assert (res["nfev"][0], res["njev"][0]) == (o["nfev"], o["njev"]), name
+        if nfev is not None:
+            assert (res["nfev"][0], res["njev"][0]) == (nfev, nfev), name
+        if name in ("gtol", "max_nfev-1"):
+            assert np.array_equal(cam[0], sc["cam"]) and np.array_equal(X, sc["X"]), name
+        elif name == "max_nfev-2":
+            print(f"camera {kind}: single-step tolerance {gr.single_step_tol(kind):.3e}")
+            assert dx <= gr.single_step_tol(kind), name
+        else:
+            assert dx <= 1e-6, name
+
+
+def test_least_squares_ba_drop_in_vs_scipy_camera_a(sfm, gpu):
+    """test_least_squares_ba_drop_in_vs_scipy on camera A (fx != fy, cx != cy != 0)."""
+    s = gr.dropin_scene(0)
+    x0 = gr.x_of(s)
+    A = og.ba_sparse(500, len(x0), 6)
+    r = least_squares(og.reprojection_error, x0, jac_sparsity=A, x_scale="jac", ftol=1e-8, args=(s["K"], s["pts"]))
+    g = sfm.least_squares_ba(x0, s["K"], s["pts"])
+    print("camera A drop-in: nfev", g.nfev, r.nfev, "|dx| / max |x|", np.abs(g.x - r.x).max() / np.abs(r.x).max())
+    assert g.success and r.success
+    assert abs(g.nfev - r.nfev) <= 1
+    assert np.abs(g.x - r.x).max() <= 1e-6 * np.abs(r.x).max()
+    assert abs(g.cost - r.cost) <= 1e-6 * r.cost + 1e-12
+    np.testing.assert_allclose(g.fun, og.reprojection_error(g.x, s["K"], s["pts"]), rtol=1e-9, atol=1e-9)
+
+
+def test_unchanged_sfm_py_least_squares_through_sfmhip_camera_a(sfm, gpu):
+    """test_unchanged_sfm_py_least_squares_through_sfmhip on camera A."""
+    import sfmhip as cv2
+    s = gr.dropin_scene(1)
+    x0 = gr.x_of(s)
+    A = cv2.ba_sparse(500, len(x0), 6)
+    got = least_squares(_sfm_py_residual(cv2), x0, jac_sparsity=A, x_scale="jac", ftol=1e-8, args=(s["K"], s["pts"]))
+    ref = least_squares(og.reprojection_error, x0, jac_sparsity=og.ba_sparse(500, len(x0), 6), x_scale="jac",
+                        ftol=1e-8, args=(s["K"], s["pts"]))
+    print("camera A sfm.py: nfev", got.nfev, ref.nfev, "|dx| / max |x|", np.abs(got.x - ref.x).max() / np.abs(ref.x).max())
     assert got.success and ref.success
     assert abs(got.nfev - ref.nfev) <= 1
     assert np.abs(got.x - ref.x).max() <= 1e-6 * np.abs(ref.x).max()

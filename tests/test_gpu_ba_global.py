@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import ba_global_ref as ref
+from geom_ref import scene_a_k, scene_b_k
 from oracle import geometry as og
 
 pytestmark = pytest.mark.gpu
@@ -74,7 +75,7 @@ def check(name, gpu, f64, ld):
     assert e_gpu <= MARGIN * e_f64, (name, e_gpu, e_f64)
 
 
-@pytest.mark.parametrize("make", [scene_a, scene_b, scene_chunks, scene_repeats])
+@pytest.mark.parametrize("make", [scene_a, scene_b, scene_chunks, scene_repeats, scene_a_k, scene_b_k])
 def test_linearize_and_blocks(sfm, gpu, make):
     s = make()
     lin = sfm.ba_global_linearize(s["cam"], s["K"], s["X"], s["obs_cam"], s["obs_pt"], s["pts2d"])
@@ -85,9 +86,7 @@ def test_linearize_and_blocks(sfm, gpu, make):
     check(f"{make.__name__} cost", np.array([lin["cost"]]), f64["cost"], ld["cost"])
 
 
-@pytest.mark.parametrize("lam", [1e-4, 1.0])
-def test_schur_matvec_matches_dense_product(sfm, gpu, lam):
-    s = scene_a()
+def _schur_matvec_matches_dense_product(sfm, s, lam):
     fixed = s["cam_fixed"]
     lin = sfm.ba_global_linearize(s["cam"], s["K"], s["X"], s["obs_cam"], s["obs_pt"], s["pts2d"])
     x = np.random.default_rng(16).standard_normal((6, 6))
@@ -99,6 +98,17 @@ def test_schur_matvec_matches_dense_product(sfm, gpu, lam):
     got64 = ref.schur_matvec(x, lam, f["U"], f["V"], f["Jc"], f["Jp"], f["oc"], f["op"], f["pt_off"], f["cam_perm"],
                              f["cam_off"], fixed)
     check(f"S({lam}) x", out, got64, want)
+
+
+@pytest.mark.parametrize("lam", [1e-4, 1.0])
+def test_schur_matvec_matches_dense_product(sfm, gpu, lam):
+    _schur_matvec_matches_dense_product(sfm, scene_a(), lam)
+
+
+@pytest.mark.parametrize("lam", [1e-4, 1.0])
+def test_schur_matvec_matches_dense_product_per_camera_K(sfm, gpu, lam):
+    """Scene A with a camera matrix per camera (geom_ref.scene_a_k: A, B, C cycling, jittered)."""
+    _schur_matvec_matches_dense_product(sfm, scene_a_k(), lam)
 
 
 def _camera_steps(cam0, cam1):
@@ -133,7 +143,7 @@ def test_one_damped_solve_meets_the_cg_tolerance(sfm, gpu):
     assert resid <= bound
 
 
-@pytest.mark.parametrize("make", [scene_a, scene_b])
+@pytest.mark.parametrize("make", [scene_a, scene_b, scene_a_k, scene_b_k])
 def test_whole_solve(sfm, gpu, make):
     """gtol = 1e-6, cameras 0 and 1 fixed; ftol = 0 so that only the gtol rule can end the
     solve (with the default 1e-10 it ends with status 2 first, see test_ba_global_cpu.py)."""
@@ -150,7 +160,7 @@ def test_whole_solve(sfm, gpu, make):
     gmax = float(max(np.abs(gc).max(), np.abs(gp).max()))
     print("max |g| recomputed", gmax)
     assert gmax <= 2 * gtol
-    if make is scene_a:
+    if make in (scene_a, scene_a_k):
         opt = ref.scipy_optimum(*args)
         print("cost - scipy", float(cost - opt["cost"]), "bound", opt["bound"])
         assert cost - opt["cost"] <= opt["bound"]
