@@ -122,6 +122,10 @@ SIGNATURES = {
     "sfmhip_sgm_aggregate": [_p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p],
     "sfmhip_volume_select": [_p, _p, _p, _i32, _i32, _i32, _p, _p, _i32, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p,
                              _p],
+    "sfmhip_sift_pyramid": [_p, _i32, _i32, _i32, _i32, _p, _p, _p, _p],
+    "sfmhip_sift_detect": [_p, _i32, _i32, _i32, _i32, _p, _i32, _f32, _f32, _f32, _i32, _p, _p, _p],
+    "sfmhip_sift_orient": [_p, _i32, _i32, _i32, _i32, _p, _p, _i32, _p, _i32, _p, _p, _p],
+    "sfmhip_sift_describe": [_p, _i32, _i32, _i32, _i32, _p, _p, _i32, _p, _p, _p, _p, _p],
     "sfmhip_find_essential": [_p, _p, _p, _i32, _p, _f64, _f64, _i32, _p, _p, _p, _p, _p, _p, _p],
     "sfmhip_recover_pose": [_p, _i64, _p, _p, _p, _i32, _p, _p, _f64, _p, _p, _p, _p, _p],
     "sfmhip_pnp_ransac": [_p, _p, _p, _i32, _p, _i32, _f64, _f64, _p, _p, _p, _p, _p, _p, _p, _p],

@@ -860,6 +860,130 @@ int sfmhip_depth_consistency(const float* depth, const float* poses, const float
                              const int32_t* refs, const int32_t* srcs, int R, int S, float eps,
                              int min_consistent, uint8_t* count, float* filtered, void* stream);
 
+/* ---- V11: SIFT keypoints and descriptors (build-defined) ---------------------
+ * Scale-space extrema, orientation and the 128-d descriptor of V grey images, in
+ * four calls.  The reference has no counterpart (it reads features from disk).
+ * Restated in numpy by tests/sift_ref.py.  V10's rule holds: every f32 operation
+ * is one IEEE round-to-nearest step in the order written, no FMA; sqrt and / are
+ * correctly rounded; sums of floats have the order written; no floating-point
+ * atomics: every output is defined to the bit and two runs give the same bits.
+ * No device exp / atan2 / cos: Gaussian taps, window tables and the cos/sin table
+ * are inputs (built in f64 on the host and rounded to f32; features.sift_tables()),
+ * the angle is the polynomial turn() below.
+ *
+ * Constants: S = 3 intervals, L = S + 3 = 6 Gaussian levels and S + 2 DoG levels per
+ * octave, O octaves (1 <= O <= 16, min(H, W) >> (O - 1) >= 1).  Octave o has
+ * H_o = ((H - 1) >> o) + 1 rows and W_o = ((W - 1) >> o) + 1 columns (octave 0 is the
+ * image: no doubling).  Pixel centres are at integer coordinates.
+ *
+ * Pyramid buffer pyr [V][per] f32 with per = L sum_o H_o W_o: level s of octave o of
+ * view v starts at v per + off_o + s H_o W_o, off_o = L sum_{j<o} H_j W_j, row-major.
+ *
+ * 1 Pyramid (sfmhip_sift_pyramid).  taps [L][27] f32 (device): row s holds the
+ *   2 r_s + 1 taps of blur s, the rest of the row is unused; radii [L] i32 is HOST
+ *   memory, 0 <= r_s <= 13.  blur(src, s): rows first, tmp[y][x] = acc after
+ *   acc = 0; for k = 0 .. 2r: acc = acc + tap[k] src[y][clamp(x + k - r, 0, W_o - 1)];
+ *   then columns, dst[y][x] likewise over tmp[clamp(y + k - r, 0, H_o - 1)][x].
+ *   Level 0 of octave 0 = blur(f32(img), 0); level s = blur(level s - 1, s);
+ *   level 0 of octave o + 1 = level S of octave o at rows 2y and columns 2x.
+ *   (The wrapper's taps: sig[s] = 1.6 2^(s/S); blur 0 has sigma sqrt(sig[0]^2 - 0.25),
+ *   blur s sqrt(sig[s]^2 - sig[s-1]^2); r = ceil(4 sigma); exp(-k^2 / (2 sigma^2))
+ *   normalised to sum 1 in f64.)
+ *
+ * 2 Detect (sfmhip_sift_detect).  D(l, y, x) = G[l+1][y][x] - G[l][y][x], formed on
+ *   the fly.  A sample (o, l, y, x) with 1 <= l <= S, border <= y <= H_o - 1 - border,
+ *   border <= x <= W_o - 1 - border starts a candidate iff |D| > prethresh and D is
+ *   strictly greater than all 26 neighbours in (l, y, x) or strictly less than all.
+ *   Refinement, at most 5 times at the current integer (l, y, x), with D.. = D there:
+ *     gx = (D(x+1) - D(x-1)) 0.5, gy and gl likewise along y and l;
+ *     c2 = 2 D; hxx = (D(x+1) + D(x-1)) - c2, hyy and hll likewise;
+ *     hxy = ((D(y+1,x+1) - D(y+1,x-1)) - (D(y-1,x+1) - D(y-1,x-1))) 0.25, hxl with
+ *     (l, x) and hyl with (l, y) in the places of (y, x);
+ *     A00 = hyy hll - hyl hyl; A01 = hxl hyl - hxy hll; A02 = hxy hyl - hxl hyy;
+ *     A11 = hxx hll - hxl hxl; A12 = hxy hxl - hxx hyl; A22 = hxx hyy - hxy hxy;
+ *     det = (hxx A00 + hxy A01) + hxl A02; reject unless |det| > 0 (NaN rejects);
+ *     ox = -(((A00 gx + A01 gy) + A02 gl) / det); oy = -(((A01 gx + A11 gy) + A12 gl) / det);
+ *     ol = -(((A02 gx + A12 gy) + A22 gl) / det);
+ *     converged iff |ox| < 0.5, |oy| < 0.5 and |ol| < 0.5: stop.  Otherwise reject
+ *     unless all three are <= 1048576 in magnitude (NaN rejects), move by
+ *     (rint(ol), rint(oy), rint(ox)) and reject if the new sample violates the
+ *     bounds of a start sample.  Not converged after the 5th solve: reject.
+ *   At the converged sample: resp = D + 0.5 ((gx ox + gy oy) + gl ol); reject if
+ *   |resp| 3.0 < contrast_thr (the wrapper passes f32(contrast 255)); tr = hxx + hyy;
+ *   d2 = hxx hyy - hxy hxy; reject if d2 <= 0 or (tr tr) edge_r >= ((edge_r + 1)
+ *   (edge_r + 1)) d2 (a NaN on either side rejects).  The scale in octave pixels,
+ *   from sig [L] f32 (device): sc = sig[l] + ol (sig[l+1] - sig[l]) if ol >= 0, else
+ *   sig[l] + ol (sig[l] - sig[l-1]).
+ *   Record, 8 32-bit words: octave (i32), level l (i32; the converged one),
+ *   x = f32(x) + ox, y = f32(y) + oy, sc, |resp|, x 2^o, y 2^o (f32).
+ *   Output rec [V][cap][8] in ascending (octave, level, row, column) of the START
+ *   sample; count [V] i32 holds the true total; only the first cap records are
+ *   written, the rest of rec stays untouched.  Count, scan, write; no atomics.
+ *
+ * turn(y, x) in turns, in [0, 1): a = |x|, b = |y|, m = max(a, b), t = min(a, b) / m
+ *   (0 if m == 0); u = t t; p = ((((C4 u + C3) u + C2) u + C1) u + C0) t with C0..C4 =
+ *   0x1.45e8e8p-3, -0x1.aec82ap-5, 0x1.d67172p-6, -0x1.bd6ba4p-7, 0x1.b4a748p-9;
+ *   if b > a: p = 0.25 - p; if signbit(x): p = 0.5 - p; if signbit(y): p = 1 - p;
+ *   if p >= 1: p = 0.  Within 2^-18 turn of atan2 (tests/test_sift_cpu.py).
+ *
+ * sample(G, px, py), bilinear with clamped indices, G one level (H_o x W_o):
+ *   x0 = floor(px); fx = px - x0; i0 = clamp(int(min(max(x0, -1), W_o)), 0, W_o - 1),
+ *   i1 = clamp(int(min(max(x0, -1), W_o)) + 1, 0, W_o - 1) (min/max as fminf/fmaxf);
+ *   y0, fy, j0, j1 likewise; top = G[j0][i0] (1 - fx) + G[j0][i1] fx, bot with j1;
+ *   value = top (1 - fy) + bot fy.
+ *
+ * 3 Orient (sfmhip_sift_orient), per record k < min(count[v], cap), on level l of
+ *   its octave: h = (sc 4.5) 0.125; P[i][j] = sample(x + f32(j - 9) h, y + f32(i - 9) h),
+ *   i, j = 0..18.  For i, j = 1..17: gx = P[i][j+1] - P[i][j-1]; gy = P[i+1][j] -
+ *   P[i-1][j]; w = sqrt(gx gx + gy gy) wo[i-1][j-1] (wo [17][17] f32, device; the
+ *   wrapper's Gaussian of sigma 1.5 sc = 8/3 samples); bin = min(int(floor(turn(gy,
+ *   gx) 36)), 35); the histogram is an INTEGER sum: hist[bin] += int(rint(min(w 1024,
+ *   4194304))) in i32 (fminf: a NaN counts as the bound).  As f32 it is smoothed
+ *   twice: h'[b] = (h[b-1] + h[b+1]) 0.25 + h[b] 0.5, circular.  With M its maximum,
+ *   bin b is a peak iff h[b] > h[b-1], h[b] > h[b+1] and h[b] >= 0.8 M; its
+ *   orientation is q = int(rint(((f32(b) + 0.5 + 0.5 (h[b-1] - h[b+1]) / ((h[b-1] - 2
+ *   h[b]) + h[b+1])) 1024) / 36)) mod 1024, in units of 1/1024 turn.  The first 4 peaks
+ *   in ascending bin order give one oriented record each: the record with word 1
+ *   replaced by l | (q << 8).  Output orec [V][cap_o][8], records in input order;
+ *   ocount [V] the true total, the first cap_o written, the rest untouched.
+ *
+ * 4 Describe (sfmhip_sift_describe), per oriented record k < min(ocount[v], cap_o):
+ *   (c, s) = cs[q] (cs [1024][2] f32, device: cos and sin of q/1024 turn);
+ *   h = (sc 12) 0.0625; u = f32(j) - 8.5, v = f32(i) - 8.5, P[i][j] = sample(x + ((u c)
+ *   - (v s)) h, y + ((u s) + (v c)) h), i, j = 0..17.  For i, j = 1..16 (a = i - 1,
+ *   b = j - 1): gx, gy as in step 3; m = sqrt(gx gx + gy gy) wd[a][b] (wd [16][16]
+ *   f32, device: Gaussian of sigma 8 samples about (7.5, 7.5)); ob = turn(gy, gx) 8;
+ *   o0 = floor(ob); fo = ob - o0; orientation bins int(o0) mod 8 with weight 1 - fo
+ *   and (int(o0) + 1) mod 8 with weight fo.  cw [4][16] f32 (device): cw[k][a] =
+ *   max(0, 1 - |(a - 1.5)/4 - k|), the bilinear weight of sample a in cell k.  Bin
+ *   (ky, kx, o), index (ky 4 + kx) 8 + o: d = the sum, added in row-major order of
+ *   (a, b) from 0, of ((m cw[ky][a]) cw[kx][b]) wgt_o(a, b); terms that are 0 may be
+ *   skipped.  n = sqrt(sum_{bin ascending} d d) (acc = acc + d d from 0); all-zero
+ *   output unless n > 0; e = min(d / n, 0.2); n' likewise over e;
+ *   desc[bin] = u8(min(rint(512 (e / n')), 255)).  Output desc [V][cap_o][128] u8;
+ *   rows at and beyond min(ocount[v], cap_o) stay untouched.
+ *
+ * Limits: 1 <= O <= 16 with min(H, W) >> (O - 1) >= 1, H W < 2^31, 0 <= V <= 65535,
+ * cap >= 0, cap_o >= 0, V cap and V cap_o below 2^28 (2^24 for the descriptors),
+ * border >= 1, radii in [0, 13]: otherwise SFMHIP_E_ARG, like a null
+ * pointer, without touching the GPU.  V = 0 is a no-op without a launch; cap = 0
+ * still counts.  An octave with H_o or W_o < 2 border + 1 holds no start sample.
+ * Records handed to steps 3 and 4 must have 0 <= octave < O, 1 <= l <= S and finite
+ * floats (what step 2 writes); rec, orec, the tables and pyr are device memory.
+ * Plain asynchronous launches on the stream; scratch from the library pool.       */
+int sfmhip_sift_pyramid(const uint8_t* img, int V, int H, int W, int O, const float* taps /* [6][27] */,
+                        const int32_t* radii /* HOST [6] */, float* pyr, void* stream);
+int sfmhip_sift_detect(const float* pyr, int V, int H, int W, int O, const float* sig /* [6] */, int border,
+                       float prethresh, float contrast_thr, float edge_r, int cap,
+                       int32_t* rec /* [V][cap][8] */, int32_t* count /* [V] */, void* stream);
+int sfmhip_sift_orient(const float* pyr, int V, int H, int W, int O, const int32_t* rec, const int32_t* count,
+                       int cap, const float* wo /* [17][17] */, int cap_o, int32_t* orec /* [V][cap_o][8] */,
+                       int32_t* ocount /* [V] */, void* stream);
+int sfmhip_sift_describe(const float* pyr, int V, int H, int W, int O, const int32_t* orec,
+                         const int32_t* ocount, int cap_o, const float* wd /* [16][16] */,
+                         const float* cw /* [4][16] */, const float* cs /* [1024][2] */,
+                         uint8_t* desc /* [V][cap_o][128] */, void* stream);
+
 /* ---- §8f row 2: geometric verification (batched over image pairs) --------
  * cv2.findEssentialMat(pts0, pts1, K, method=cv2.RANSAC, prob=0.999,
  * threshold=1) at matching.py:134 and sfm.py:108 (OpenCV five-point.cpp +
