@@ -73,6 +73,11 @@ SIGNATURES = {
                                      _p],
     "sfmhip_match_pairs_exact_fp6_i16": [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _i32, _i32, _i32, _p,
                                          _p, _p],
+    "sfmhip_match_key_values": [_p, _i32, _i32, _p, _p, _p],
+    "sfmhip_match_pairs_exact_fp6_kv": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _i32, _i32, _i32, _p,
+                                        _p, _p],
+    "sfmhip_match_pairs_exact_fp6_kv_i16": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _i32, _i32, _i32,
+                                            _p, _p, _p],
     "sfmhip_vq": [_p, _i64, _p, _i32, _i32, _p, _p, _p],
     "sfmhip_word_histogram": [_p, _p, _i32, _i32, _p, _p],
     "sfmhip_kmeans_update": [_p, _i64, _i32, _p, _i32, _p, _p, _p],

@@ -113,14 +113,15 @@ __global__ void prepare_kernel(const int8_t* __restrict__ desc, int n_rows, int 
     keys[row] = (r < nk[img]) ? (-s * 128 + low) : (INT_MIN + low);
 }
 
-// h = keys >> 8 (match_kernel's value-only form), one call's scratch; hf (nullable) = the same values in
-// f32 for match_fp6_kernel's accumulator chains (|h| <= 2^23: the conversion is exact).
+// h = keys >> 8 (match_kernel's value-only form); hf (nullable) = h / 64 in f32, the chain starts of
+// match_fp6_kernel in its unit 2^-6 (|h| <= 2^23 and the factor is a power of two: exact).  Both depend on
+// the bank alone: sfmhip_match_key_values builds them once, the entries without them once per call.
 __global__ void key_values_kernel(const int32_t* __restrict__ keys, int64_t n, int32_t* __restrict__ h,
                                   float* __restrict__ hf) {
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
         const int v = keys[e] >> 8;
         h[e] = v;
-        if (hf) hf[e] = (float)v;
+        if (hf) hf[e] = (float)v * 0.015625f;
     }
 }
 
@@ -676,14 +677,18 @@ __global__ __launch_bounds__(64 * WAVES, 2) void match_kernel(
 
 // ---------------------------------------------------------------------------
 // match_fp6_kernel (DESIGN.md K1''): the value-only form of match_kernel (16x16 tiles) with the filter's
-// dot products on v_mfma_scale_f32_16x16x128_f8f6f4 (twice the int8 rate per clock).  The operands are
-// the e2m3 codes of the grid values g (quantize_fp6_kernel; value g / 8) under the unit block scale 2^3
-// (E8M0 byte 130 in every byte of the scale register, so the op_sel byte does not matter): every
-// product is the integer g_a g_b.  |sum g_a g_b| <= D * 3600 <= 921,600 and h_j >= -2^23, so every
-// partial sum of  acc = <b_j, a_i> + h_j  is an integer below 2^24 in magnitude: exact in f32 whatever
-// the order the array sums in, and the identities of the value-only form (match_kernel's comment) hold
+// dot products on v_mfma_f32_16x16x128_f8f6f4 (twice the int8 rate per clock).  The operands are the e2m3
+// codes of the grid values g (quantize_fp6_kernel; value g / 8) as they stand: both block scales are the
+// constant 0, for which the compiler emits the unscaled 8-byte instruction (measured 6.6 % faster in
+// registers than the scaled one under the unit scale 2^3: profiles/r12/mx_probe_unscaled.txt), and every
+// product is g_a g_b / 64.  The loop therefore runs in units of 2^-6: the chains start from h_j / 64
+// (key_values_kernel's hf).  |sum g_a g_b| <= D * 3600 <= 921,600 and h_j >= -2^23, so every partial sum
+// of  acc = (<b_j, a_i> + h_j) / 64  is an integer multiple of 2^-6 below 2^18 in magnitude: 24 significant
+// bits, exact in f32 whatever the order the array sums in, and a positive power-of-two factor changes no
+// maximum, median or comparison: the identities of the value-only form (match_kernel's comment) hold
 // as they stand, with g in place of q.  The loop's maxima run in f32 (no conversion per distance); the
-// row's top two are converted to int once after the loop (exact) and value_only_tail takes over: its
+// row's top two are multiplied by 64 and converted to int once after the loop (both exact) and
+// value_only_tail takes over on the integers <b_j, a_i> + h_j: its
 // rescan dots the int8 rows g.  Same LDS ring, XCD remap, candidate blocks and ranges as match_kernel.
 // The block loop is software-pipelined by one tile (fp6_sched.h): a tile's maxima and a range's merge
 // issue in the gaps between the following MFMAs, in an order the source pins.
@@ -816,10 +821,10 @@ __global__ __launch_bounds__(64 * kFp6Waves, 2) void match_fp6_kernel(
     const int32_t* __restrict__ pairs, int n_iblk, int nwg, long long rn2, long long rd2,
     OutT* __restrict__ m0, CertArgs ca) {
     constexpr int MF = 16, NS = kFp6Tiles, WAVES = kFp6Waves, VG = kValueOnlyTiles;
-    static_assert(D % 128 == 0, "one scaled MFMA takes 128 elements of k");
+    static_assert(D % 128 == 0, "one MFMA takes 128 elements of k");
     static_assert(NS % 4 == 0, "value_only_tail takes four query tiles at a time");
     using S = DenseStager<D, WAVES>;
-    constexpr int KK = D / 128;                     // scaled MFMAs per output tile
+    constexpr int KK = D / 128;                     // MFMAs per output tile
     using SC = Fp6Sched<KK, NS>;
     static_assert(kJB / MF == 2 * VG, "two ranges per block: the range maxima alternate between two sets");
     static_assert(SC::merge(VG * SC::MPT, 0) == -1, "a range's gaps hold the previous range's merge");
@@ -828,8 +833,8 @@ __global__ __launch_bounds__(64 * kFp6Waves, 2) void match_fp6_kernel(
     constexpr int NT = 64 * WAVES;
     constexpr int IW = MF * NS, IB = IW * WAVES;
     constexpr int JT = kJB / MF;
-    constexpr int kScale = (int)0x82828282;         // E8M0 2^3 in every byte
-    constexpr float kLow = -16777216.f;             // below every value (padded rows: -2^23)
+    constexpr int kScale = 0;                       // both scales the constant 0: the unscaled instruction
+    constexpr float kLow = -262144.f;               // -2^18, below every value in units of 2^-6 (padded rows: -2^17)
 
     __shared__ __attribute__((aligned(16))) int8_t lds[2 * TILE + 2 * kJB * 4];
 
@@ -850,7 +855,7 @@ __global__ __launch_bounds__(64 * kFp6Waves, 2) void match_fp6_kernel(
     }
 
     const uint8_t* bdense = dense + (size_t)b * m_pad * S::ROW;
-    const int32_t* bhf = reinterpret_cast<const int32_t*>(hf) + (size_t)b * m_pad;   // f32 bits through the key DMA
+    const int32_t* bhf = reinterpret_cast<const int32_t*>(hf) + (size_t)b * m_pad;   // h / 64, f32 bits through the key DMA
     const int nblk = (nb_rows + kJB - 1) / kJB;
     int32_t* kbase = reinterpret_cast<int32_t*>(lds + 2 * TILE);
 
@@ -986,9 +991,13 @@ __global__ __launch_bounds__(64 * kFp6Waves, 2) void match_fp6_kernel(
     // value_only_tail decides 64 query rows (four tiles, one per lane group) per call
 #pragma unroll
     for (int q = 0; q < NS / 4; ++q) {
-        int v1[4], v2[4], vr[4];   // integers below 2^24 in magnitude: the conversion is exact
+        int v1[4], v2[4], vr[4];   // back to integers below 2^24 in magnitude (kLow: -2^24): product and conversion exact
 #pragma unroll
-        for (int s = 0; s < 4; ++s) { v1[s] = (int)w1[4 * q + s]; v2[s] = (int)w2[4 * q + s]; vr[s] = wr[4 * q + s]; }
+        for (int s = 0; s < 4; ++s) {
+            v1[s] = (int)(64.f * w1[4 * q + s]);
+            v2[s] = (int)(64.f * w2[4 * q + s]);
+            vr[s] = wr[4 * q + s];
+        }
         value_only_tail<D, MF, 4, VG, OutT>(v1, v2, vr, g, g + (size_t)b * m_pad * D, h + (size_t)b * m_pad, norms, a, b,
                                             m_pad, na_rows, ibase + q * 4 * MF, grp, lr, lane, rn2, rd2, out_m, ca);
     }
@@ -2255,10 +2264,12 @@ static int match_exact_impl(const int8_t* desc, const int32_t* norms, const int3
                             const double* resid_img, int mode, const int32_t* n_kpts, int n_img,
                             int m_pad, int d, const int32_t* pairs, int P, int ratio_num, int ratio_den,
                             OutT* matches0, int32_t* dist1, int32_t* dist2, uint32_t* n_resolved,
-                            void* stream, const uint8_t* dense = nullptr) {
+                            void* stream, const uint8_t* dense = nullptr, const int32_t* h_bank = nullptr,
+                            const float* hf_bank = nullptr) {
     // dense: the packed e2m3 codes of desc (sfmhip_desc_pack_fp6; the sfmhip_match_pairs_exact_fp6 entries:
     // desc = desc_q = the grid values g, mode 1, no distance outputs); SFMHIP_MATCH_FP6=0 runs the int8
-    // value-only kernel on g instead
+    // value-only kernel on g instead.  h_bank / hf_bank: the bank's key values (sfmhip_match_key_values; the
+    // _kv entries), else they are built from keys in this call's scratch
     const bool fp6 = dense && knobs().match_fp6 != 0;
     if (dense) {
         SFMHIP_REQUIRE(mode == 1 && !dist1 && !dist2 && (d == 128 || d == 256),
@@ -2299,7 +2310,8 @@ static int match_exact_impl(const int8_t* desc, const int32_t* norms, const int3
     // no distance outputs (the int16 graph; dist.match_all_pairs_sharded): the value-only form
     const bool value_only = !dist1 && !dist2;
     const size_t rbytes = 2 * rlist_bytes + rcnt_bytes + roff_bytes + ritem_bytes;   // a multiple of 4
-    const size_t hn = value_only ? (size_t)n_img * m_pad : 0;   // the value-only form's h = keys >> 8, behind the rest
+    // the value-only form's h = keys >> 8, behind the rest unless the caller brought the bank's
+    const size_t hn = value_only && !h_bank ? (size_t)n_img * m_pad : 0;
     if (scratch_alloc(&rbuf, rbytes + hn * (fp6 ? 2 : 1) * sizeof(int32_t), s) != hipSuccess) {
         (void)hipGetLastError();
         set_error("sfmhip_match_pairs_exact: scratch allocation failed");
@@ -2320,13 +2332,15 @@ static int match_exact_impl(const int8_t* desc, const int32_t* norms, const int3
         return check_launch("memset");
     }
     const int rxgrid = n_cu * 2;   // a multiple of 8: every XCD gets the same number of blocks
-    float* hf = nullptr;
+    const float* hf = hf_bank;
+    if (h_bank) keys = h_bank;
     if (hn) {
         int32_t* h = reinterpret_cast<int32_t*>(static_cast<char*>(rbuf) + rbytes);
-        hf = fp6 ? reinterpret_cast<float*>(h + hn) : nullptr;   // the same values in f32, behind h
+        float* hf_call = fp6 ? reinterpret_cast<float*>(h + hn) : nullptr;   // h / 64 in f32, behind h
         hipLaunchKernelGGL(key_values_kernel, dim3(std::min(ceil_div((int64_t)hn, 256), 4096)), dim3(256), 0, s, keys,
-                           (int64_t)hn, h, hf);
+                           (int64_t)hn, h, hf_call);
         keys = h;
+        hf = hf_call;
     }
 #define SFMHIP_LAUNCH_EXACT(DD)                                                                                  \
     if (fp6) {                                                                                                    \
@@ -2414,4 +2428,39 @@ extern "C" int sfmhip_match_pairs_exact_fp6_i16(const uint8_t* dense, const int8
     return match_exact_impl(g, norms, keys, g, desc_f, resid_row, resid_img, 1, n_kpts, n_img, m_pad, d, pairs, P,
                             ratio_num, ratio_den, matches0, (int32_t*)nullptr, (int32_t*)nullptr, n_resolved, stream,
                             dense);
+}
+
+// The key values of a bank, built once (key_values_kernel): h = keys >> 8 and hf = h / 64 in f32, both
+// [n_img][m_pad], from the keys of sfmhip_desc_prepare on g.  They depend on the bank alone; the _kv match
+// entries take them in place of a rebuild over all n_img m_pad keys on every call.
+extern "C" int sfmhip_match_key_values(const int32_t* keys, int n_img, int m_pad, int32_t* h, float* hf, void* stream) {
+    SFMHIP_REQUIRE(keys && h && hf, "sfmhip_match_key_values: null pointer");
+    SFMHIP_REQUIRE(n_img > 0 && m_pad > 0, "sfmhip_match_key_values: bad shape");
+    const int64_t n = (int64_t)n_img * m_pad;
+    hipLaunchKernelGGL(key_values_kernel, dim3(std::min(ceil_div(n, 256), 4096)), dim3(256), 0, as_stream(stream), keys, n,
+                       h, hf);
+    return check_launch("key_values_kernel");
+}
+
+extern "C" int sfmhip_match_pairs_exact_fp6_kv(const uint8_t* dense, const int8_t* g, const int32_t* norms,
+                                               const int32_t* h, const float* hf, const float* desc_f,
+                                               const double* resid_row, const double* resid_img, const int32_t* n_kpts,
+                                               int n_img, int m_pad, int d, const int32_t* pairs, int P, int ratio_num,
+                                               int ratio_den, int32_t* matches0, uint32_t* n_resolved, void* stream) {
+    SFMHIP_REQUIRE((dense && hf) || P == 0, "sfmhip_match_pairs_exact_fp6_kv: null pointer");
+    return match_exact_impl(g, norms, h, g, desc_f, resid_row, resid_img, 1, n_kpts, n_img, m_pad, d, pairs, P,
+                            ratio_num, ratio_den, matches0, (int32_t*)nullptr, (int32_t*)nullptr, n_resolved, stream,
+                            dense, h, hf);
+}
+
+extern "C" int sfmhip_match_pairs_exact_fp6_kv_i16(const uint8_t* dense, const int8_t* g, const int32_t* norms,
+                                                   const int32_t* h, const float* hf, const float* desc_f,
+                                                   const double* resid_row, const double* resid_img,
+                                                   const int32_t* n_kpts, int n_img, int m_pad, int d,
+                                                   const int32_t* pairs, int P, int ratio_num, int ratio_den,
+                                                   int16_t* matches0, uint32_t* n_resolved, void* stream) {
+    SFMHIP_REQUIRE((dense && hf) || P == 0, "sfmhip_match_pairs_exact_fp6_kv_i16: null pointer");
+    return match_exact_impl(g, norms, h, g, desc_f, resid_row, resid_img, 1, n_kpts, n_img, m_pad, d, pairs, P,
+                            ratio_num, ratio_den, matches0, (int32_t*)nullptr, (int32_t*)nullptr, n_resolved, stream,
+                            dense, h, hf);
 }

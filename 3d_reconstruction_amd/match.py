@@ -114,7 +114,8 @@ class DescriptorBank:
             self._nres = torch.zeros(1, dtype=torch.int32, device=q.device)
         # FP6 certified filter (DESIGN.md K1''): the grid values g, their e2m3 codes, the dense operand rows the
         # kernel reads and g's norms, keys and residual bounds, built once (the descriptors do not change between
-        # match calls); +2.75 bytes per element
+        # match calls); +2.75 bytes per element.  gh / ghf: the key values the filter's chains start from
+        # (h = gkeys >> 8 and h / 64 in f32), which the entries without them rebuild over the whole bank per call
         self.code = None
         self.dense = None
         if x is not None and self.mode == MODE_FLOAT and self.d % 128 == 0:
@@ -130,6 +131,10 @@ class DescriptorBank:
                  ptr(self.gnorms), ptr(self.gkeys), stream_ptr())
             call("sfmhip_desc_residual", ptr(self.x), ptr(self.g), self.n_img, self.m_pad, self.d, ptr(self.n_kpts),
                  self.mode, ptr(self.gerow), ptr(self.geimg), stream_ptr())
+            self.gh = torch.empty_like(self.gkeys)
+            self.ghf = torch.empty(self.gkeys.shape, dtype=torch.float32, device=q.device)
+            call("sfmhip_match_key_values", ptr(self.gkeys), self.n_img, self.m_pad, ptr(self.gh), ptr(self.ghf),
+                 stream_ptr())
 
     @property
     def device(self) -> torch.device:
@@ -228,10 +233,10 @@ class DescriptorBank:
         exact = getattr(self, "_exact_now", False) if exact is None else exact
         i16 = m0.dtype == torch.int16
         if exact and d1 is None and self.dense is not None:   # the FP6 filter (SFMHIP_MATCH_FP6=0: int8 on g)
-            call("sfmhip_match_pairs_exact_fp6_i16" if i16 else "sfmhip_match_pairs_exact_fp6", ptr(self.dense),
-                 ptr(self.g), ptr(self.gnorms), ptr(self.gkeys), ptr(self.x), ptr(self.gerow), ptr(self.geimg),
-                 ptr(self.n_kpts), self.n_img, self.m_pad, self.d, ptr(pr), int(pr.shape[0]), num, den, ptr(m0),
-                 ptr(self._nres), stream_ptr())
+            call("sfmhip_match_pairs_exact_fp6_kv_i16" if i16 else "sfmhip_match_pairs_exact_fp6_kv", ptr(self.dense),
+                 ptr(self.g), ptr(self.gnorms), ptr(self.gh), ptr(self.ghf), ptr(self.x), ptr(self.gerow),
+                 ptr(self.geimg), ptr(self.n_kpts), self.n_img, self.m_pad, self.d, ptr(pr), int(pr.shape[0]), num, den,
+                 ptr(m0), ptr(self._nres), stream_ptr())
             self.last_resolved = self._nres
             return
         if exact and i16:

@@ -195,6 +195,24 @@ int sfmhip_match_pairs_exact_fp6_i16(const uint8_t* dense, const int8_t* g, cons
                                      int d, const int32_t* pairs, int P, int ratio_num, int ratio_den,
                                      int16_t* matches0, uint32_t* n_resolved, void* stream);
 
+/* The two entries above derive, on every call, the key values of the whole bank
+ * from `keys`: h = keys >> 8 (int32) and hf = h / 64 (f32, exact: |h| <= 2^23),
+ * both [n_img][m_pad], the chain starts of the filter.  They depend on the bank
+ * alone.  sfmhip_match_key_values builds them once from the keys of
+ * sfmhip_desc_prepare on g; the _kv entries take them in place of `keys` and
+ * are otherwise the entries above: the same graph and n_resolved.              */
+int sfmhip_match_key_values(const int32_t* keys, int n_img, int m_pad, int32_t* h, float* hf, void* stream);
+int sfmhip_match_pairs_exact_fp6_kv(const uint8_t* dense, const int8_t* g, const int32_t* norms,
+                                    const int32_t* h, const float* hf, const float* desc_f,
+                                    const double* resid_row, const double* resid_img, const int32_t* n_kpts,
+                                    int n_img, int m_pad, int d, const int32_t* pairs, int P, int ratio_num,
+                                    int ratio_den, int32_t* matches0, uint32_t* n_resolved, void* stream);
+int sfmhip_match_pairs_exact_fp6_kv_i16(const uint8_t* dense, const int8_t* g, const int32_t* norms,
+                                        const int32_t* h, const float* hf, const float* desc_f,
+                                        const double* resid_row, const double* resid_img, const int32_t* n_kpts,
+                                        int n_img, int m_pad, int d, const int32_t* pairs, int P, int ratio_num,
+                                        int ratio_den, int16_t* matches0, uint32_t* n_resolved, void* stream);
+
 /* ---- M2: scipy.cluster.vq.vq (matching.py:27, bow.py:23) ---------------
  * codes[i] = argmin_c sum_k (obs[i,k]-code[c,k])^2 (lowest index on ties),
  * dist[i] = sqrt(min).  f64 throughout.                                      */

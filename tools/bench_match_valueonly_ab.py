@@ -1,7 +1,7 @@
 """Interleaved A/B of builds of libsfmhip.so on the C3 exact-float match step (257 x 4096 x
 256-d, int16 graph: the call dist.match_all_pairs_sharded makes), in one process on one device:
 
-    python tools/bench_match_valueonly_ab.py [--rounds N] [--entry NAME] [--other-entry NAME] OTHER_LIB.so [...]
+    python tools/bench_match_valueonly_ab.py [--rounds N] [--entry NAME] [--other-entry NAME] [--d D] OTHER_LIB.so [...]
 
 The other libraries (e.g. the parent commit's build under another file name) and the tree's
 library all run on the same bank (quantised operands, keys and residual bounds of the tree's
@@ -14,7 +14,7 @@ sfmhip_match_pairs_exact_i16 on the int8 operands, so a parent build without the
 other arm, unless --other-entry sfmhip_match_pairs_exact_fp6_i16 sends them through their FP6 entry
 too.  An FP6 arm gets the operand array its library reads: the dense rows (bank.dense) when the library
 exports sfmhip_desc_pack_fp6, the 32-byte chunks of the quantiser (bank.code) when it does not — a
-parent build from before the dense layout."""
+parent build from before the dense layout.  --d 128 runs the step on 257 x 4096 x 128-d descriptors."""
 import ctypes
 import hashlib
 import importlib
@@ -40,6 +40,9 @@ if args and args[0] == "--entry":
 OTHER_NAME = NAME
 if args and args[0] == "--other-entry":
     OTHER_NAME, args = args[1], args[2:]
+D = 256
+if args and args[0] == "--d":
+    D, args = int(args[1]), args[2:]
 FP6_NAME = "sfmhip_match_pairs_exact_fp6_i16"
 if TREE_NAME not in (NAME, FP6_NAME) or OTHER_NAME not in (NAME, FP6_NAME):
     raise SystemExit(f"--entry and --other-entry must be {NAME} or {FP6_NAME}")
@@ -52,13 +55,13 @@ for path in args:
 arms.append(("tree", abi.lib))
 
 dev = torch.device("cuda", 0)
-x = syn.superpoint_like(257, 4096, 256, seed=1, device=dev)
+x = syn.superpoint_like(257, 4096, D, seed=1, device=dev)
 bank = sfm.DescriptorBank.from_float(x, mode=sfm.MODE_FLOAT)
 del x
 allp = sfm.all_pairs(257)
 near = allp[(allp[:, 1] - allp[:, 0]) <= 2]
 ptr, sp = abi.ptr, abi.stream_ptr
-print(f"device {torch.cuda.get_device_name(0)}, rounds {rounds}", flush=True)
+print(f"device {torch.cuda.get_device_name(0)}, rounds {rounds}, d {D}", flush=True)
 for label, pairs in (("full", allp), ("near", near)):
     pr = abi.dev(pairs, torch.int32)
     P = int(pr.shape[0])
@@ -99,5 +102,6 @@ for label, pairs in (("full", allp), ("near", near)):
         h = hashlib.sha256(outs[n].cpu().numpy().tobytes()).hexdigest()[:16]
         print(f"{label} ({P} pairs) {n}: median {np.median(t):.3f} ms  min {t.min():.3f}  max {t.max():.3f}  "
               f"rows_rescored {res[n]}  graph sha {h}", flush=True)
+        print(f"    rounds in order: {' '.join(f'{v:.3f}' for v in t)}", flush=True)
     del outs
     torch.cuda.empty_cache()

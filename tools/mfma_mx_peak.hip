@@ -18,6 +18,11 @@
 // Build: hipcc -O3 --offload-arch=gfx950 -o tools/mfma_mx_peak tools/mfma_mx_peak.hip
 // Run:   tools/mfma_mx_peak ITERS   (a multiple of 4)
 //        tools/mfma_mx_peak ITERS tile8   (a multiple of 8): only the two arms of kern_fp6_tile8
+//        tools/mfma_mx_peak ITERS unscaled   the gate of DESIGN K1'' round 12: first the numerics of the FP6
+//                                         MFMA with both scales 0 (the compiler then emits the plain 8-byte
+//                                         v_mfma_f32_16x16x128_f8f6f4) on codes of known grid values, then
+//                                         the scaled and unscaled forms of kern_fp6_tile8 and of the 32x32x64
+//                                         shape, interleaved
 #include <hip/hip_runtime.h>
 #include <climits>
 #include <cstdio>
@@ -200,12 +205,16 @@ struct Op6 {
     __device__ i32x8 tuple() const { return i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], 0, 0}; }
     __device__ void set(int e, int x) { if (e < 4) lo[e] = x; else hi[e - 4] = x; }
 };
-template <int PIPE>
+// SCALED 1: unit block scale 2^3 on both sides, integer products.  SCALED 0: both scales 0, which the compiler
+// emits as the unscaled instruction; the products are g_a g_b / 64, so the chain starts and kLow are divided by
+// 64 and the top two multiplied by 64 at the end (all exact): the checksum is the scaled form's.
+template <int PIPE, int SCALED = 1>
 __global__ __launch_bounds__(256, 2) void kern_fp6_tile8(const int* __restrict__ seed, int iters, int* out) {
     constexpr int NS = 8, KK = 2, VG = 4;
     using SC = sfmhip::Fp6Sched<KK, NS>;
-    constexpr int kScale = (int)0x82828282;
-    const float kLow = -16777216.f;
+    constexpr int kScale = SCALED ? (int)0x82828282 : 0;
+    constexpr float kUnit = SCALED ? 1.f : 0.015625f, kBack = SCALED ? 1.f : 64.f;
+    const float kLow = -16777216.f * kUnit;
     const int lane = threadIdx.x & 63;
     Op6 a[KK], b[NS][KK];   // 32 codes = 24 bytes in 6 registers, as the kernel holds them
 #pragma unroll
@@ -217,7 +226,7 @@ __global__ __launch_bounds__(256, 2) void kern_fp6_tile8(const int* __restrict__
             for (int t = 0; t < NS; ++t) b[t][k].set(e, seed[(blockIdx.x * 31 + lane * 5 + k * 11 + e * 3 + t * 17) & 4095]);
         }
     f32x4 hv;
-    for (int e = 0; e < 4; ++e) hv[e] = (float)(seed[(lane * 3 + e) & 4095] >> 9);
+    for (int e = 0; e < 4; ++e) hv[e] = (float)(seed[(lane * 3 + e) & 4095] >> 9) * kUnit;
     float f1[NS], f2[NS], rm[2][NS], half[NS];
     int wr[NS];
     bool up[NS];
@@ -306,25 +315,183 @@ __global__ __launch_bounds__(256, 2) void kern_fp6_tile8(const int* __restrict__
     }
     int r = 0;
 #pragma unroll
-    for (int t = 0; t < NS; ++t) r += (int)f1[t] + (int)f2[t] + wr[t];
+    for (int t = 0; t < NS; ++t) r += (int)(f1[t] * kBack) + (int)(f2[t] * kBack) + wr[t];
 #undef MERGE_STEP
-    out[blockIdx.x * blockDim.x + threadIdx.x] = r;   // the same value in both arms
+    out[blockIdx.x * blockDim.x + threadIdx.x] = r;   // the same value in every arm
 }
 
-// the two arms of the real shape, interleaved, REPS times each: per-arm min / median / max and the checksum
-static int run_tile8(const int* seed, int* out, int blocks, int iters) {
+// The same output area per wave (2048 distances of d = 256 per tile step) on v_mfma_scale_f32_32x32x64_f8f6f4:
+// 2 chains x 4 k-steps, the candidates on the 16 accumulator registers, so a tile's maxima are 8 max3 per
+// chain and a range's merge 4 instructions per chain.  Compiler order.  Measured for the record only.
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+template <int SCALED>
+__global__ __launch_bounds__(256, 2) void kern_fp6_32x32(const int* __restrict__ seed, int iters, int* out) {
+    constexpr int NS = 2, KK = 4, VG = 4;
+    constexpr int kScale = SCALED ? (int)0x82828282 : 0;
+    constexpr float kUnit = SCALED ? 1.f : 0.015625f, kBack = SCALED ? 1.f : 64.f;
+    const float kLow = -16777216.f * kUnit;
+    const int lane = threadIdx.x & 63;
+    Op6 a[KK], b[NS][KK];
+#pragma unroll
+    for (int k = 0; k < KK; ++k)
+#pragma unroll
+        for (int e = 0; e < 6; ++e) {
+            a[k].set(e, seed[(blockIdx.x * 97 + lane * 13 + k * 7 + e) & 4095]);
+#pragma unroll
+            for (int t = 0; t < NS; ++t) b[t][k].set(e, seed[(blockIdx.x * 31 + lane * 5 + k * 11 + e * 3 + t * 17) & 4095]);
+        }
+    f32x16 hv;
+    for (int e = 0; e < 16; ++e) hv[e] = (float)(seed[(lane * 3 + e) & 4095] >> 9) * kUnit;
+    float f1[NS], f2[NS], rm[NS];
+    int wr[NS];
+    bool up[NS];
+#pragma unroll
+    for (int t = 0; t < NS; ++t) { f1[t] = f2[t] = rm[t] = kLow; wr[t] = 0; up[t] = false; }
+    for (int it = 0; it < iters; it += 2 * VG) {
+#pragma unroll
+        for (int jt = 0; jt < 2 * VG; ++jt) {
+            const int R = jt / VG, tt = jt % VG;
+            asm volatile("" : "+v"(hv));
+#pragma unroll
+            for (int k = 0; k < KK; ++k) asm volatile("" : "+v"(a[k].lo), "+v"(a[k].hi));
+            f32x16 acc[NS];
+#pragma unroll
+            for (int t = 0; t < NS; ++t) acc[t] = hv;
+#pragma unroll
+            for (int k = 0; k < KK; ++k)
+#pragma unroll
+                for (int t = 0; t < NS; ++t)
+                    acc[t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[k].tuple(), b[t][k].tuple(), acc[t], 2, 2, 0,
+                                                                             kScale, 0, kScale);
+#pragma unroll
+            for (int t = 0; t < NS; ++t) {
+                if (tt == 0) rm[t] = kLow;
+#pragma unroll
+                for (int e = 0; e < 16; e += 2) rm[t] = __builtin_fmaxf(__builtin_fmaxf(rm[t], acc[t][e]), acc[t][e + 1]);
+            }
+            if (tt == VG - 1) {
+                const int rid = (it >> 2) + R;
+#pragma unroll
+                for (int t = 0; t < NS; ++t)
+#pragma unroll
+                    for (int step = 0; step < 4; ++step) sfmhip::fp6_merge_step(step, rm[t], rid, up[t], f1[t], f2[t], wr[t]);
+            }
+        }
+    }
+    int r = 0;
+#pragma unroll
+    for (int t = 0; t < NS; ++t) r += (int)(f1[t] * kBack) + (int)(f2[t] * kBack) + wr[t];
+    out[blockIdx.x * blockDim.x + threadIdx.x] = r;
+}
+
+// Numerics of one 16 x 16 x 256 tile (two chained MFMAs, as the kernel's KK = 2) on codes the host chose:
+// lane (grp, lr) gives codes 32 grp .. 32 grp + 31 of k-step k of row lr on both sides; the chains start from
+// c0[row]; out[row][col], row = 4 grp + register (the A side), col = lr (the B side).
+template <int SCALED>
+__global__ void kern_fp6_check(const int* __restrict__ ca, const int* __restrict__ cb, const float* __restrict__ c0,
+                               float* __restrict__ out) {
+    constexpr int kScale = SCALED ? (int)0x82828282 : 0;
+    const int lane = threadIdx.x & 63, grp = lane / 16, lr = lane % 16;
+    Op6 a[2], b[2];
+    for (int k = 0; k < 2; ++k)
+        for (int e = 0; e < 6; ++e) {
+            a[k].set(e, ca[((lr * 2 + k) * 4 + grp) * 6 + e]);
+            b[k].set(e, cb[((lr * 2 + k) * 4 + grp) * 6 + e]);
+        }
+    f32x4 acc;
+    for (int e = 0; e < 4; ++e) acc[e] = c0[4 * grp + e];
+    for (int k = 0; k < 2; ++k)
+        acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[k].tuple(), b[k].tuple(), acc, 2, 2, 0, kScale, 0, kScale);
+    for (int e = 0; e < 4; ++e) out[(4 * grp + e) * 16 + lr] = acc[e];
+}
+
+// grid value g (value g / 8) of an e2m3 code
+static int fp6_g(int code) {
+    const int n = code & 31, ex = n >> 3, m = n & 7;
+    const int g = ex == 0 ? m : (8 + m) << (ex - 1);
+    return code & 32 ? -g : g;
+}
+
+// Every output of the form with the given scale argument must equal (sum g_a g_b) * unit + c0 exactly.
+// Rows 0 / 1 hold +60 / -60 throughout (|dot| = 921,600 at both signs), row 2 alternates them, the rest are
+// random codes; c0 runs from -2^23 (the padded rows' start) upwards, in the form's unit.
+static int check_numerics(int scaled) {
+    static int code[2][16][256];
+    unsigned x = 2463534242u;
+    for (int side = 0; side < 2; ++side)
+        for (int r = 0; r < 16; ++r)
+            for (int k = 0; k < 256; ++k) {
+                x = x * 1664525u + 1013904223u;
+                code[side][r][k] = r == 0 ? 31 : r == 1 ? 63 : r == 2 ? (k & 1 ? 63 : 31) : (int)(x >> 26);
+            }
+    const double unit = scaled ? 1.0 : 1.0 / 64;
+    static int packed[2][16 * 2 * 4 * 6];
+    memset(packed, 0, sizeof(packed));
+    for (int side = 0; side < 2; ++side)
+        for (int r = 0; r < 16; ++r)
+            for (int k = 0; k < 256; ++k) {   // code e of a 32-chunk at bits 6 e .. 6 e + 5 of its 24 bytes
+                const int chunk = k / 32, e = k % 32, bit = 6 * e;
+                unsigned char* bytes = reinterpret_cast<unsigned char*>(&packed[side][(r * 8 + chunk) * 6]);
+                const unsigned v = (unsigned)code[side][r][k] << (bit & 7);
+                bytes[bit >> 3] |= v & 0xff;
+                if (v >> 8) bytes[(bit >> 3) + 1] |= v >> 8;
+            }
+    float c0[16], host[256];
+    for (int r = 0; r < 16; ++r) c0[r] = (float)((r == 3 ? -8388608.0 : r == 4 ? 0.0 : -(double)(r * 524287 % 8388608)) * unit);
+    int *da, *db;
+    float *dc, *dout;
+    hipMalloc(&da, sizeof(packed[0]));
+    hipMalloc(&db, sizeof(packed[1]));
+    hipMalloc(&dc, sizeof(c0));
+    hipMalloc(&dout, sizeof(host));
+    hipMemcpy(da, packed[0], sizeof(packed[0]), hipMemcpyHostToDevice);
+    hipMemcpy(db, packed[1], sizeof(packed[1]), hipMemcpyHostToDevice);
+    hipMemcpy(dc, c0, sizeof(c0), hipMemcpyHostToDevice);
+    if (scaled) hipLaunchKernelGGL(kern_fp6_check<1>, dim3(1), dim3(64), 0, 0, da, db, dc, dout);
+    else hipLaunchKernelGGL(kern_fp6_check<0>, dim3(1), dim3(64), 0, 0, da, db, dc, dout);
+    if (hipMemcpy(host, dout, sizeof(host), hipMemcpyDeviceToHost) != hipSuccess) { printf("check launch failed\n"); return 1; }
+    int bad = 0;
+    double ratio_lo = 1e300, ratio_hi = -1e300;
+    for (int i = 0; i < 16; ++i)
+        for (int j = 0; j < 16; ++j) {
+            long long dot = 0;
+            for (int k = 0; k < 256; ++k) dot += (long long)fp6_g(code[0][i][k]) * fp6_g(code[1][j][k]);
+            const double want = (double)dot * unit + (double)c0[i];   // exact in double
+            const double got = (double)host[i * 16 + j];
+            if (got != want) {
+                if (bad++ < 8) printf("  MISMATCH [%d][%d]: dot %lld start %.6f want %.6f got %.6f\n", i, j, dot, (double)c0[i], want, got);
+            }
+            if (dot != 0) {   // the factor the hardware put on g_a g_b
+                const double ratio = (got - (double)c0[i]) / (double)dot;
+                ratio_lo = ratio < ratio_lo ? ratio : ratio_lo;
+                ratio_hi = ratio > ratio_hi ? ratio : ratio_hi;
+            }
+        }
+    printf("numerics, %s: out[0][0] %.6f (dot 921600) out[0][1] %.6f (dot -921600); implied factor on g_a g_b in [%.10g, %.10g] "
+           "(expected %.10g); %d of 256 outputs differ from (sum g_a g_b) * %g + start\n",
+           scaled ? "scales 0x82828282 (scaled form)" : "scales 0 (unscaled form)", (double)host[0] - (double)c0[0],
+           (double)host[1] - (double)c0[0], ratio_lo, ratio_hi, unit, bad, unit);
+    hipFree(da); hipFree(db); hipFree(dc); hipFree(dout);
+    return bad != 0;
+}
+
+// arms of the real shape, interleaved, REPS times each: per-arm min / median / max and the checksum
+struct Arm {
+    const char* name;
+    void (*kern)(const int*, int, int*);
+    int group;   // arms of one group compute the same checksum
+};
+static int run_arms(const Arm* arms, int n_arms, const int* seed, int* out, int blocks, int iters, float (*ms)[7]) {
     const int REPS = 7;
-    float ms[2][REPS];
-    long long sum[2] = {0, 0};
+    long long sum[8] = {0};
     hipEvent_t e0, e1;
     hipEventCreate(&e0);
     hipEventCreate(&e1);
     int* host = (int*)malloc((size_t)blocks * 256 * 4);
     for (int rep = -1; rep < REPS; ++rep)   // rep -1 warms up
-        for (int arm = 0; arm < 2; ++arm) {
+        for (int arm = 0; arm < n_arms; ++arm) {
             hipEventRecord(e0);
-            if (arm == 0) hipLaunchKernelGGL(kern_fp6_tile8<0>, dim3(blocks), dim3(256), 0, 0, seed, iters, out);
-            else hipLaunchKernelGGL(kern_fp6_tile8<1>, dim3(blocks), dim3(256), 0, 0, seed, iters, out);
+            hipLaunchKernelGGL(arms[arm].kern, dim3(blocks), dim3(256), 0, 0, seed, iters, out);
             hipEventRecord(e1);
             if (hipEventSynchronize(e1) != hipSuccess) { printf("launch failed\n"); return 1; }
             if (rep < 0) {
@@ -335,22 +502,53 @@ static int run_tile8(const int* seed, int* out, int blocks, int iters) {
             }
         }
     free(host);
-    // per wave: iters tiles x 8 chains x 16 x 16 outputs x d = 256 x 2 ops; 16 MFMAs per tile
+    // per wave: iters tiles x 8 chains x 16 x 16 outputs x d = 256 x 2 ops; 16 MFMAs of 16x16x128 per tile
     const double ops = (double)blocks * 4 * iters * 8.0 * 16 * 16 * 256 * 2;
     const double mfma_per_simd = (double)blocks * 4 * iters * 16 / (256.0 * 4);
-    const char* names[2] = {"clustered (compiler order)", "pipelined (Fp6Sched order)"};
-    for (int arm = 0; arm < 2; ++arm) {
+    bool equal = true;
+    for (int arm = 0; arm < n_arms; ++arm) {
         float* m = ms[arm];
         for (int i = 0; i < REPS; ++i)
             for (int j = i + 1; j < REPS; ++j)
                 if (m[j] < m[i]) { float t = m[i]; m[i] = m[j]; m[j] = t; }
-        printf("fp6 8 chains x 2 k-steps, %-27s: min %.3f  median %.3f  max %.3f ms  %6.0f TOPS at the median, "
-               "%.1f ns per MFMA per SIMD, checksum %lld\n",
-               names[arm], m[0], m[REPS / 2], m[REPS - 1], ops / m[REPS / 2] / 1e9, m[REPS / 2] * 1e6 / mfma_per_simd,
+        printf("fp6 %-50s: min %.3f  median %.3f  max %.3f ms  %6.0f TOPS at the median, "
+               "%.1f ns per 16x16x128 of work per SIMD, checksum %lld\n",
+               arms[arm].name, m[0], m[REPS / 2], m[REPS - 1], ops / m[REPS / 2] / 1e9, m[REPS / 2] * 1e6 / mfma_per_simd,
                sum[arm]);
+        for (int o = 0; o < arm; ++o)
+            if (arms[o].group == arms[arm].group && sum[o] != sum[arm]) equal = false;
     }
-    printf("checksums %s\n", sum[0] == sum[1] ? "equal" : "DIFFER");
-    return sum[0] == sum[1] ? 0 : 1;
+    printf("checksums %s\n", equal ? "equal" : "DIFFER");
+    return equal ? 0 : 1;
+}
+
+static int run_tile8(const int* seed, int* out, int blocks, int iters) {
+    const Arm arms[2] = {{"8 chains x 2 k-steps, clustered (compiler order)", kern_fp6_tile8<0>, 0},
+                         {"8 chains x 2 k-steps, pipelined (Fp6Sched order)", kern_fp6_tile8<1>, 0}};
+    float ms[2][7];
+    return run_arms(arms, 2, seed, out, blocks, iters, ms);
+}
+
+// The gate: numerics first (a form that does not multiply the codes as they stand closes the lever), then
+// the scaled and unscaled forms interleaved.
+static int run_unscaled(const int* seed, int* out, int blocks, int iters) {
+    if (check_numerics(1)) { printf("the scaled form is not exact: the probe itself is wrong\n"); return 1; }
+    if (check_numerics(0)) { printf("GATE: the unscaled form does not give g_a g_b / 64 exactly: lever closed\n"); return 1; }
+    const Arm arms[6] = {{"16x16x128 scaled,   clustered (compiler order)", kern_fp6_tile8<0, 1>, 0},
+                         {"16x16x128 unscaled, clustered (compiler order)", kern_fp6_tile8<0, 0>, 0},
+                         {"16x16x128 scaled,   pipelined (Fp6Sched order)", kern_fp6_tile8<1, 1>, 0},
+                         {"16x16x128 unscaled, pipelined (Fp6Sched order)", kern_fp6_tile8<1, 0>, 0},
+                         {"32x32x64  scaled,   clustered (compiler order)", kern_fp6_32x32<1>, 1},
+                         {"32x32x64  unscaled, clustered (compiler order)", kern_fp6_32x32<0>, 1}};
+    float ms[6][7];
+    if (run_arms(arms, 6, seed, out, blocks, iters, ms)) return 1;
+    for (int p = 0; p < 4; p += 2)   // sorted by run_arms
+        printf("GATE %s: unscaled max %.3f ms %s scaled min %.3f ms (medians %.3f vs %.3f: %+.2f %%)\n",
+               p ? "pipelined" : "clustered", ms[p + 1][6], ms[p + 1][6] < ms[p][0] ? "<" : ">=", ms[p][0], ms[p + 1][3], ms[p][3],
+               100.0 * (ms[p + 1][3] / ms[p][3] - 1.0));
+    printf("32x32x64 against 16x16x128, scaled, medians: %.3f vs %.3f ms (%+.2f %%)\n", ms[4][3], ms[0][3],
+           100.0 * (ms[4][3] / ms[0][3] - 1.0));
+    return 0;
 }
 
 int main(int argc, char** argv) {
@@ -366,6 +564,7 @@ int main(int argc, char** argv) {
     }
     hipMemcpy(seed, h, sizeof(h), hipMemcpyHostToDevice);
     if (argc > 2 && !strcmp(argv[2], "tile8")) return run_tile8(seed, out, blocks, iters & ~7);
+    if (argc > 2 && !strcmp(argv[2], "unscaled")) return run_unscaled(seed, out, blocks, iters & ~7);
     // per wave-iteration: 4 tiles x 16 x 16 outputs x d = 256 x 2 ops
     const double ops_iter = 4.0 * 16 * 16 * 256 * 2;
     const char* names[8] = {"int8 16x16x64 (today)", "int8 16x16x64 (today)", "fp6 e2m3 16x16x128 scaled",
