@@ -93,6 +93,10 @@ SIGNATURES = {
     "sfmhip_ba_global_schur_matvec": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _f64, _p, _p, _p],
     "sfmhip_ba_global": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _f64, _f64, _f64, _i32, _i32, _p, _p,
                          _p],
+    "sfmhip_ba_global_linearize_robust": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _p, _p, _p, _p, _p, _p,
+                                          _p, _p, _p, _i32, _f64, _p],
+    "sfmhip_ba_global_robust": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _f64, _f64, _f64, _i32, _i32,
+                                _p, _p, _p, _i32, _f64, _p],
     "sfmhip_voxel_traversal_count": [_p, _i64, _f32, _i32, _p, _p],
     "sfmhip_voxel_traversal": [_p, _i64, _f32, _i32, _p, _p],
     "sfmhip_voxel_traversal_capped": [_p, _i64, _f32, _i32, _p, _p, _p],

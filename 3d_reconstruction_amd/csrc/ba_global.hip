@@ -15,6 +15,8 @@
 // The host enqueues one LM trial (damping, right-hand side, max_cg CG iterations, back
 // substitution, trial cost, step control) and reads one control record back; kernels return at
 // once when the record says `done` / `cg_done`.
+// A robust loss (huber, soft_l1, cauchy; tests/ba_robust_ref.py) lives in k_linearize alone: plain
+// IRLS, the stored r, Jc, Jp carry sqrt(w) and the cost sums f^2 rho, nothing downstream changes.
 #include "common.h"
 #include "geom_dev.h"
 #include <climits>
@@ -29,6 +31,7 @@ constexpr int kChunk = 256;            // observations per camera chunk (= one p
 constexpr double kFloor = 1e-12;       // floor of a damped diagonal entry
 constexpr double kLambda0 = 1e-4, kLambdaMin = 1e-12, kLambdaMax = 1e12;
 enum { kMatvec = 0, kRhs = 1, kBacksub = 2 };
+enum { kLinear = 0, kHuber = 1, kSoftL1 = 2, kCauchy = 3 };   // loss codes of the C ABI
 
 struct Ctl {
     double lambda, cost, cost_trial, rel, rz, bb, gtol, ftol, eta;
@@ -55,6 +58,8 @@ struct Ws {                            // device pointers of one solve
     double *U, *gc, *V, *gp, *Us, *Ui, *Vi;
     double *part27, *part6, *y;
     double *b, *x, *rr, *z, *p, *q;    // CG vectors (6C each)
+    double f2;                         // robust loss: f_scale^2
+    double* wout;                      // nullable: the IRLS weight per sorted observation
 };
 
 __device__ __forceinline__ bool is_fixed(const uint8_t* f, int c) { return f != nullptr && f[c] != 0; }
@@ -203,8 +208,26 @@ __global__ __launch_bounds__(kWg) void k_init(Ws w, const double* cam, const dou
         for (int k = 0; k < 3; ++k) w.X[3 * i + k] = X[3 * i + k];
 }
 
+// rho'(z) and rho(z) of the robust losses (scipy's definitions), z = |r|^2 / f^2 of one observation.
+template <int LOSS>
+__device__ __forceinline__ double loss_weight(double z) {
+    if (LOSS == kHuber) return z <= 1.0 ? 1.0 : 1.0 / sqrt(z);
+    if (LOSS == kSoftL1) return 1.0 / sqrt(1.0 + z);
+    return 1.0 / (1.0 + z);
+}
+
+template <int LOSS>
+__device__ __forceinline__ double loss_rho(double z) {
+    if (LOSS == kHuber) return z <= 1.0 ? z : 2.0 * sqrt(z) - 1.0;
+    if (LOSS == kSoftL1) return 2.0 * (sqrt(1.0 + z) - 1.0);
+    return log1p(z);
+}
+
 // Residual, Jacobians (JAC) and the workgroup's partial cost, one lane per sorted observation.
-template <bool JAC>
+// LOSS = kLinear: r, Jc, Jp and |r|^2 as they are.  A robust LOSS (plain IRLS): with z = |r|^2 / f^2
+// and w = rho'(z) the stored arrays are sqrt(w) r, sqrt(w) Jc, sqrt(w) Jp and the cost term is
+// f^2 rho(z), so everything downstream reads the robust Gauss-Newton quantities unchanged.
+template <bool JAC, int LOSS>
 __global__ __launch_bounds__(kWg) void k_linearize(Ws w, const double* Rs, const double* ts, const double* Xs,
                                                    bool trial) {
     if (w.ctl->bad || (trial && w.ctl->done)) return;
@@ -227,34 +250,86 @@ __global__ __launch_bounds__(kWg) void k_linearize(Ws w, const double* Rs, const
         const double xn = x * iz, yn = y * iz;
         const double r0 = (xn * fx + cx) - w.uv[2 * m], r1 = (yn * fy + cy) - w.uv[2 * m + 1];
         sq = r0 * r0 + r1 * r1;
+        double sw = 1.0;                   // sqrt(w); not read when LOSS == kLinear
+        if (LOSS != kLinear) {
+            const double zr = sq / w.f2;
+            sq = w.f2 * loss_rho<LOSS>(zr);
+            if (JAC) {
+                const double wt = loss_weight<LOSS>(zr);
+                if (w.wout != nullptr) w.wout[m] = wt;
+                sw = sqrt(wt);
+            }
+        }
         if (JAC) {
-            w.r[2 * m] = r0;
-            w.r[2 * m + 1] = r1;
             const double a = fx * iz, b = fy * iz;
             const double d02 = -(a * xn), d12 = -(b * yn);
             double* Jp = w.Jp + 6 * m;
+            double* Jc = w.Jc + 12 * m;
+            double jp[6], jc[12];
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
-                Jp[j] = a * R[j] + d02 * R[6 + j];
-                Jp[3 + j] = b * R[3 + j] + d12 * R[6 + j];
+                jp[j] = a * R[j] + d02 * R[6 + j];
+                jp[3 + j] = b * R[3 + j] + d12 * R[6 + j];
             }
-            double* Jc = w.Jc + 12 * m;
-            Jc[0] = d02 * py;
-            Jc[1] = a * pz - d02 * px;
-            Jc[2] = -(a * py);
-            Jc[3] = a;
-            Jc[4] = 0.0;
-            Jc[5] = d02;
-            Jc[6] = -(b * pz) + d12 * py;
-            Jc[7] = -(d12 * px);
-            Jc[8] = b * px;
-            Jc[9] = 0.0;
-            Jc[10] = b;
-            Jc[11] = d12;
+            jc[0] = d02 * py;
+            jc[1] = a * pz - d02 * px;
+            jc[2] = -(a * py);
+            jc[3] = a;
+            jc[4] = 0.0;
+            jc[5] = d02;
+            jc[6] = -(b * pz) + d12 * py;
+            jc[7] = -(d12 * px);
+            jc[8] = b * px;
+            jc[9] = 0.0;
+            jc[10] = b;
+            jc[11] = d12;
+            if (LOSS == kLinear) {
+                w.r[2 * m] = r0;
+                w.r[2 * m + 1] = r1;
+#pragma unroll
+                for (int j = 0; j < 6; ++j) Jp[j] = jp[j];
+#pragma unroll
+                for (int j = 0; j < 12; ++j) Jc[j] = jc[j];
+            } else {
+                w.r[2 * m] = sw * r0;
+                w.r[2 * m + 1] = sw * r1;
+#pragma unroll
+                for (int j = 0; j < 6; ++j) Jp[j] = sw * jp[j];
+#pragma unroll
+                for (int j = 0; j < 12; ++j) Jc[j] = sw * jc[j];
+            }
         }
     }
     const double s = block_sum(sq, sm);
     if (threadIdx.x == 0) w.cpart[blockIdx.x] = s;
+}
+
+// The unweighted |r|^2 of every sorted observation at (Rs, ts, Xs): k_linearize's residual, once
+// after the solve.
+__global__ __launch_bounds__(kWg) void k_obs_res2(Ws w, const double* Rs, const double* ts, const double* Xs,
+                                                  double* res2) {
+    if (w.ctl->bad) return;
+    const int64_t m = (int64_t)blockIdx.x * kWg + threadIdx.x;
+    if (m >= w.M) return;
+    const int c = w.oc[m], p = w.op[m];
+    const double* R = Rs + 9 * (int64_t)c;
+    const double* t = ts + 3 * (int64_t)c;
+    const double* X = Xs + 3 * (int64_t)p;
+    const double* K = w.K + 9 * (int64_t)c;
+    const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
+    const double px = (R[0] * X[0] + R[1] * X[1]) + R[2] * X[2];
+    const double py = (R[3] * X[0] + R[4] * X[1]) + R[5] * X[2];
+    const double pz = (R[6] * X[0] + R[7] * X[1]) + R[8] * X[2];
+    const double x = px + t[0], y = py + t[1], z = pz + t[2];
+    const double iz = 1.0 / z;
+    const double xn = x * iz, yn = y * iz;
+    const double r0 = (xn * fx + cx) - w.uv[2 * m], r1 = (yn * fy + cy) - w.uv[2 * m + 1];
+    res2[m] = r0 * r0 + r1 * r1;
+}
+
+__global__ __launch_bounds__(kWg) void k_fill(double* out, int64_t n, double v) {
+    const int64_t i = (int64_t)blockIdx.x * kWg + threadIdx.x;
+    if (i < n) out[i] = v;
 }
 
 // cost = 0.5 sum of the partial costs (infinite after a non-positive depth); one workgroup.
@@ -769,9 +844,21 @@ void launch_validate(const Ws& w, hipStream_t st) {
     hipLaunchKernelGGL(k_chunks, dim3(1), dim3(1), 0, st, w);
 }
 
+// k_linearize<JAC, loss>; the linear loss is its own instantiation with today's operations only.
+template <bool JAC>
+void launch_residuals(const Ws& w, int loss, const double* R, const double* t, const double* X, bool trial,
+                      hipStream_t st) {
+    switch (loss) {
+    case kHuber: hipLaunchKernelGGL((k_linearize<JAC, kHuber>), dim3(w.nb), dim3(kWg), 0, st, w, R, t, X, trial); break;
+    case kSoftL1: hipLaunchKernelGGL((k_linearize<JAC, kSoftL1>), dim3(w.nb), dim3(kWg), 0, st, w, R, t, X, trial); break;
+    case kCauchy: hipLaunchKernelGGL((k_linearize<JAC, kCauchy>), dim3(w.nb), dim3(kWg), 0, st, w, R, t, X, trial); break;
+    default: hipLaunchKernelGGL((k_linearize<JAC, kLinear>), dim3(w.nb), dim3(kWg), 0, st, w, R, t, X, trial); break;
+    }
+}
+
 // Linearise at (R, t, X) of the workspace: r, Jc, Jp, the cost and the blocks.
-void launch_linearize(const Ws& w, bool solver, hipStream_t st) {
-    hipLaunchKernelGGL(k_linearize<true>, dim3(w.nb), dim3(kWg), 0, st, w, w.R, w.t, w.X, false);
+void launch_linearize(const Ws& w, int loss, bool solver, hipStream_t st) {
+    launch_residuals<true>(w, loss, w.R, w.t, w.X, false, st);
     hipLaunchKernelGGL(k_cost_final, dim3(1), dim3(kWg), 0, st, w, false);
     hipLaunchKernelGGL(k_point_blocks, dim3(grid_of(w.N)), dim3(kWg), 0, st, w, solver);
     hipLaunchKernelGGL(k_cam_partial, dim3(w.tmax), dim3(kWg), 0, st, w);
@@ -795,17 +882,24 @@ bool common_args_ok(const char* who, const void* oc, const void* op, const void*
     return true;
 }
 
-}  // namespace
-}  // namespace sfmhip
+bool loss_args_ok(const char* who, int loss, double f_scale) {
+    if (loss < kLinear || loss > kCauchy) {
+        set_error("%s: unknown loss code %d (0 linear, 1 huber, 2 soft_l1, 3 cauchy)", who, loss);
+        return false;
+    }
+    if (!(f_scale > 0.0) || !std::isfinite(f_scale)) {
+        set_error("%s: f_scale must be positive and finite", who);
+        return false;
+    }
+    return true;
+}
 
-using namespace sfmhip;
-
-extern "C" int sfmhip_ba_global_linearize(const double* cam, const double* K, const double* X, const int32_t* obs_cam,
-                                          const int32_t* obs_pt, const double* pts2d, const int64_t* pt_off,
-                                          const int64_t* cam_perm, const int64_t* cam_off, int C, int N, int64_t M,
-                                          double* r, double* Jc, double* Jp, double* U, double* g_c, double* V,
-                                          double* g_p, double* cost, void* stream) {
-    const char* who = "sfmhip_ba_global_linearize";
+int linearize_impl(const char* who, const double* cam, const double* K, const double* X, const int32_t* obs_cam,
+                   const int32_t* obs_pt, const double* pts2d, const int64_t* pt_off, const int64_t* cam_perm,
+                   const int64_t* cam_off, int C, int N, int64_t M, double* r, double* Jc, double* Jp, double* U,
+                   double* g_c, double* V, double* g_p, double* cost, int loss, double f_scale, double* weight,
+                   void* stream) {
+    if (!loss_args_ok(who, loss, f_scale)) return SFMHIP_E_ARG;
     if (!common_args_ok(who, obs_cam, obs_pt, pt_off, cam_perm, cam_off, C, N, M)) return SFMHIP_E_ARG;
     SFMHIP_REQUIRE(cost && (C == 0 || (cam && K && U && g_c)) && (N == 0 || (X && V && g_p)) &&
                        (M == 0 || (pts2d && r && Jc && Jp)), "%s: null pointer", who);
@@ -814,6 +908,7 @@ extern "C" int sfmhip_ba_global_linearize(const double* cam, const double* K, co
     w.K = K; w.oc = obs_cam; w.op = obs_pt; w.uv = pts2d; w.pt_off = pt_off; w.cam_perm = cam_perm; w.cam_off = cam_off;
     w.C = C; w.N = N; w.M = M;
     w.r = r; w.Jc = Jc; w.Jp = Jp; w.U = U; w.gc = g_c; w.V = V; w.gp = g_p;
+    w.f2 = f_scale * f_scale; w.wout = weight;
     void* scratch = nullptr;
     int rc = alloc_ws(who, w, false, false, false, st, &scratch);
     if (rc != SFMHIP_OK) return rc;
@@ -826,13 +921,42 @@ extern "C" int sfmhip_ba_global_linearize(const double* cam, const double* K, co
     }
     if (rc == SFMHIP_OK) {
         hipLaunchKernelGGL(k_init, dim3(grid_of(std::max(C, N))), dim3(kWg), 0, st, w, cam, X);
-        launch_linearize(w, false, st);
+        launch_linearize(w, loss, false, st);
+        if (loss == kLinear && weight != nullptr && M > 0)
+            hipLaunchKernelGGL(k_fill, dim3(grid_of(M)), dim3(kWg), 0, st, weight, M, 1.0);
         rc = check_launch("ba_global linearize");
         if (rc == SFMHIP_OK) rc = read_ctl(who, w, &h, st);
         if (rc == SFMHIP_OK) *cost = h.cost;
     }
     scratch_free(scratch, st);
     return rc;
+}
+
+}  // namespace
+}  // namespace sfmhip
+
+using namespace sfmhip;
+
+extern "C" int sfmhip_ba_global_linearize(const double* cam, const double* K, const double* X, const int32_t* obs_cam,
+                                          const int32_t* obs_pt, const double* pts2d, const int64_t* pt_off,
+                                          const int64_t* cam_perm, const int64_t* cam_off, int C, int N, int64_t M,
+                                          double* r, double* Jc, double* Jp, double* U, double* g_c, double* V,
+                                          double* g_p, double* cost, void* stream) {
+    return linearize_impl("sfmhip_ba_global_linearize", cam, K, X, obs_cam, obs_pt, pts2d, pt_off, cam_perm, cam_off, C,
+                          N, M, r, Jc, Jp, U, g_c, V, g_p, cost, kLinear, 1.0, nullptr, stream);
+}
+
+extern "C" int sfmhip_ba_global_linearize_robust(const double* cam, const double* K, const double* X,
+                                                 const int32_t* obs_cam, const int32_t* obs_pt, const double* pts2d,
+                                                 const int64_t* pt_off, const int64_t* cam_perm,
+                                                 const int64_t* cam_off, int C, int N, int64_t M, double* r, double* Jc,
+                                                 double* Jp, double* U, double* g_c, double* V, double* g_p,
+                                                 double* cost, void* stream, int loss, double f_scale, double* weight) {
+    const char* who = "sfmhip_ba_global_linearize_robust";
+    if (!loss_args_ok(who, loss, f_scale)) return SFMHIP_E_ARG;
+    SFMHIP_REQUIRE(M <= 0 || weight, "%s: null pointer", who);
+    return linearize_impl(who, cam, K, X, obs_cam, obs_pt, pts2d, pt_off, cam_perm, cam_off, C, N, M, r, Jc, Jp, U, g_c,
+                          V, g_p, cost, loss, f_scale, weight, stream);
 }
 
 extern "C" int sfmhip_ba_global_schur_matvec(const double* Jc, const double* Jp, const double* U, const double* V,
@@ -871,12 +995,14 @@ extern "C" int sfmhip_ba_global_schur_matvec(const double* Jc, const double* Jp,
     return rc;
 }
 
-extern "C" int sfmhip_ba_global(double* cam, const double* K, double* X, const int32_t* obs_cam, const int32_t* obs_pt,
-                                const double* pts2d, const int64_t* pt_off, const int64_t* cam_perm,
-                                const int64_t* cam_off, const uint8_t* cam_fixed, int C, int N, int64_t M, double gtol,
-                                double ftol, double eta, int max_iter, int max_cg, double* cost, int32_t* info,
-                                void* stream) {
-    const char* who = "sfmhip_ba_global";
+namespace sfmhip {
+namespace {
+
+int solve_impl(const char* who, double* cam, const double* K, double* X, const int32_t* obs_cam, const int32_t* obs_pt,
+               const double* pts2d, const int64_t* pt_off, const int64_t* cam_perm, const int64_t* cam_off,
+               const uint8_t* cam_fixed, int C, int N, int64_t M, double gtol, double ftol, double eta, int max_iter,
+               int max_cg, double* cost, int32_t* info, int loss, double f_scale, double* obs_res2, void* stream) {
+    if (!loss_args_ok(who, loss, f_scale)) return SFMHIP_E_ARG;
     if (!common_args_ok(who, obs_cam, obs_pt, pt_off, cam_perm, cam_off, C, N, M)) return SFMHIP_E_ARG;
     SFMHIP_REQUIRE(cost && info && (C == 0 || (cam && K)) && (N == 0 || X) && (M == 0 || pts2d), "%s: null pointer",
                    who);
@@ -886,6 +1012,7 @@ extern "C" int sfmhip_ba_global(double* cam, const double* K, double* X, const i
     Ws w = {};
     w.K = K; w.oc = obs_cam; w.op = obs_pt; w.uv = pts2d; w.pt_off = pt_off; w.cam_perm = cam_perm; w.cam_off = cam_off;
     w.fixed = cam_fixed; w.C = C; w.N = N; w.M = M;
+    w.f2 = f_scale * f_scale;
     void* scratch = nullptr;
     int rc = alloc_ws(who, w, true, true, true, st, &scratch);
     if (rc != SFMHIP_OK) return rc;
@@ -907,7 +1034,7 @@ extern "C" int sfmhip_ba_global(double* cam, const double* K, double* X, const i
     const int gcn = grid_of(std::max(C, N));
     launch_validate(w, st);
     hipLaunchKernelGGL(k_init, dim3(gcn), dim3(kWg), 0, st, w, (const double*)cam, (const double*)X);
-    launch_linearize(w, true, st);
+    launch_linearize(w, loss, true, st);
     hipLaunchKernelGGL(k_gate, dim3(1), dim3(1), 0, st, w);
     rc = check_launch("ba_global linearize");
     if (rc == SFMHIP_OK) rc = read_ctl(who, w, &h, st);
@@ -933,8 +1060,7 @@ extern "C" int sfmhip_ba_global(double* cam, const double* K, double* X, const i
         hipLaunchKernelGGL(k_point_pass, dim3(grid_of(N)), dim3(kWg), 0, st, w, (int)kBacksub, (const double*)w.x,
                            false);
         hipLaunchKernelGGL(k_trial, dim3(gcn), dim3(kWg), 0, st, w);
-        hipLaunchKernelGGL(k_linearize<false>, dim3(w.nb), dim3(kWg), 0, st, w, (const double*)w.Rt,
-                           (const double*)w.tt, (const double*)w.Xt, true);
+        launch_residuals<false>(w, loss, w.Rt, w.tt, w.Xt, true, st);
         hipLaunchKernelGGL(k_cost_final, dim3(1), dim3(kWg), 0, st, w, true);
         hipLaunchKernelGGL(k_step, dim3(1), dim3(1), 0, st, w);
         hipLaunchKernelGGL(k_accept, dim3(gcn), dim3(kWg), 0, st, w);
@@ -945,13 +1071,16 @@ extern "C" int sfmhip_ba_global(double* cam, const double* K, double* X, const i
         if (nit == max_iter) break;          // status 0
         // the next linearisation goes in front of the next trial's batch: when the gate ends the
         // solve there, that batch returns at once and the record read after it says so
-        launch_linearize(w, true, st);
+        launch_linearize(w, loss, true, st);
         hipLaunchKernelGGL(k_gate, dim3(1), dim3(1), 0, st, w);
         ++nit;
     }
     if (rc == SFMHIP_OK) {
         status = h.done ? h.status : 0;
         hipLaunchKernelGGL(k_finish, dim3(gcn), dim3(kWg), 0, st, w, cam, X);
+        if (obs_res2 != nullptr && M > 0)   // the final unweighted |r|^2, at the accepted state
+            hipLaunchKernelGGL(k_obs_res2, dim3(w.nb), dim3(kWg), 0, st, w, (const double*)w.R, (const double*)w.t,
+                               (const double*)w.X, obs_res2);
         rc = check_launch("ba_global finish");
         if (rc == SFMHIP_OK && hipStreamSynchronize(st) != hipSuccess) {
             set_error("%s: %s", who, hipGetErrorString(hipGetLastError()));
@@ -964,4 +1093,26 @@ extern "C" int sfmhip_ba_global(double* cam, const double* K, double* X, const i
     }
     scratch_free(scratch, st);
     return rc;
+}
+
+}  // namespace
+}  // namespace sfmhip
+
+extern "C" int sfmhip_ba_global(double* cam, const double* K, double* X, const int32_t* obs_cam, const int32_t* obs_pt,
+                                const double* pts2d, const int64_t* pt_off, const int64_t* cam_perm,
+                                const int64_t* cam_off, const uint8_t* cam_fixed, int C, int N, int64_t M, double gtol,
+                                double ftol, double eta, int max_iter, int max_cg, double* cost, int32_t* info,
+                                void* stream) {
+    return solve_impl("sfmhip_ba_global", cam, K, X, obs_cam, obs_pt, pts2d, pt_off, cam_perm, cam_off, cam_fixed, C, N,
+                      M, gtol, ftol, eta, max_iter, max_cg, cost, info, kLinear, 1.0, nullptr, stream);
+}
+
+extern "C" int sfmhip_ba_global_robust(double* cam, const double* K, double* X, const int32_t* obs_cam,
+                                       const int32_t* obs_pt, const double* pts2d, const int64_t* pt_off,
+                                       const int64_t* cam_perm, const int64_t* cam_off, const uint8_t* cam_fixed, int C,
+                                       int N, int64_t M, double gtol, double ftol, double eta, int max_iter, int max_cg,
+                                       double* cost, int32_t* info, void* stream, int loss, double f_scale,
+                                       double* obs_res2) {
+    return solve_impl("sfmhip_ba_global_robust", cam, K, X, obs_cam, obs_pt, pts2d, pt_off, cam_perm, cam_off, cam_fixed,
+                      C, N, M, gtol, ftol, eta, max_iter, max_cg, cost, info, loss, f_scale, obs_res2, stream);
 }

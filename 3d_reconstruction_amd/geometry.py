@@ -338,25 +338,55 @@ def _fixed_tensor(cam_fixed, C):
     return dev(f, torch.uint8)
 
 
-def ba_global_linearize(cam, K, X, obs_cam, obs_pt, pts2d) -> dict:
-    """Linearise the global problem at (cam, X) (``sfmhip_ba_global_linearize``).
+BA_LOSSES = {"linear": 0, "huber": 1, "soft_l1": 2, "cauchy": 3}
+
+
+def _ba_loss(loss, f_scale):
+    if loss not in BA_LOSSES:
+        raise ValueError(f"loss must be one of {sorted(BA_LOSSES)}, got {loss!r}")
+    return BA_LOSSES[loss], float(f_scale)
+
+
+def ba_loss_weight(e2, loss: str = "linear", f_scale: float = 1.0) -> np.ndarray:
+    """The IRLS weight rho'(z), z = e2 / f_scale^2, of squared residual norms ``e2`` (numpy; the
+    solver's own weights are computed on the device, this is for reporting)."""
+    z = np.asarray(e2, np.float64) / (float(f_scale) * float(f_scale))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if loss == "huber":
+            return np.where(z <= 1.0, 1.0, 1.0 / np.sqrt(z))
+        if loss == "soft_l1":
+            return 1.0 / np.sqrt(1.0 + z)
+        if loss == "cauchy":
+            return 1.0 / (1.0 + z)
+    _ba_loss(loss, f_scale)
+    return np.ones_like(z)
+
+
+def ba_global_linearize(cam, K, X, obs_cam, obs_pt, pts2d, loss: str = "linear", f_scale: float = 1.0) -> dict:
+    """Linearise the global problem at (cam, X) (``sfmhip_ba_global_linearize_robust``).
 
     cam (C,6) = rvec, t; K (3,3) or (C,3,3); X (N,3); one (obs_cam, obs_pt, pts2d) row
     per observation, in any order.  Returns device tensors in the SORTED order
     (``order`` maps it to the caller's list): r (M,2), Jc (M,2,6), Jp (M,2,3), and
     the blocks U (C,6,6), g_c (C,6), V (N,3,3), g_p (N,3); ``cost`` (float), and the
-    layout arrays ``sfmhip_ba_global_schur_matvec`` needs."""
+    layout arrays ``sfmhip_ba_global_schur_matvec`` needs.
+
+    With a robust ``loss`` (see :func:`bundle_adjust`) r, Jc, Jp are the weighted sqrt(w) r,
+    sqrt(w) Jc, sqrt(w) Jp, the blocks and ``cost`` the robust ones; ``weight`` (M,) is w per
+    sorted observation (1 for the linear loss)."""
     require_gpu()
+    code, f_scale = _ba_loss(loss, f_scale)
     d = _ba_global_inputs(cam, K, X, obs_cam, obs_pt, pts2d)
     C, N, M = d["C"], d["N"], d["M"]
     dv = d["cam"].device
     for name, shape in (("r", (M, 2)), ("Jc", (M, 2, 6)), ("Jp", (M, 2, 3)), ("U", (C, 6, 6)), ("g_c", (C, 6)),
-                        ("V", (N, 3, 3)), ("g_p", (N, 3))):
+                        ("V", (N, 3, 3)), ("g_p", (N, 3)), ("weight", (M,))):
         d[name] = torch.empty(shape, dtype=torch.float64, device=dv)
     cost = ctypes.c_double(0.0)
-    call("sfmhip_ba_global_linearize", ptr(d["cam"]), ptr(d["K"]), ptr(d["X"]), ptr(d["obs_cam"]), ptr(d["obs_pt"]),
-         ptr(d["pts2d"]), ptr(d["pt_off"]), ptr(d["cam_perm"]), ptr(d["cam_off"]), C, N, M, ptr(d["r"]), ptr(d["Jc"]),
-         ptr(d["Jp"]), ptr(d["U"]), ptr(d["g_c"]), ptr(d["V"]), ptr(d["g_p"]), ctypes.addressof(cost), stream_ptr())
+    call("sfmhip_ba_global_linearize_robust", ptr(d["cam"]), ptr(d["K"]), ptr(d["X"]), ptr(d["obs_cam"]),
+         ptr(d["obs_pt"]), ptr(d["pts2d"]), ptr(d["pt_off"]), ptr(d["cam_perm"]), ptr(d["cam_off"]), C, N, M, ptr(d["r"]),
+         ptr(d["Jc"]), ptr(d["Jp"]), ptr(d["U"]), ptr(d["g_c"]), ptr(d["V"]), ptr(d["g_p"]), ctypes.addressof(cost),
+         stream_ptr(), code, f_scale, ptr(d["weight"]))
     d["cost"] = cost.value
     return d
 
@@ -379,9 +409,29 @@ def ba_global_schur_matvec(lin: dict, x, lam: float, cam_fixed=None) -> torch.Te
     return out
 
 
+class _BundleResult(SimpleNamespace):
+    """bundle_adjust's result.  ``residual`` and ``weight`` are brought from the device and put into
+    the caller's order when first read, so a solve whose caller does not read them pays nothing."""
+
+    def _e2(self):
+        if not isinstance(self._res2, np.ndarray):
+            e2 = np.empty(len(self._order))
+            e2[self._order] = self._res2.cpu().numpy()      # sorted order -> the caller's
+            self._res2 = e2
+        return self._res2
+
+    @property
+    def residual(self):
+        return np.sqrt(self._e2())
+
+    @property
+    def weight(self):
+        return ba_loss_weight(self._e2(), self.loss, self.f_scale)
+
+
 def bundle_adjust(cam, K, X, obs_cam, obs_pt, pts2d, cam_fixed=None, gtol: float = 1e-8, ftol: float = 1e-10,
-                  eta: float = 1e-2, max_iter: int = 50, max_cg: int = 64):
-    """Global bundle adjustment of all cameras and points (``sfmhip_ba_global``).
+                  eta: float = 1e-2, max_iter: int = 50, max_cg: int = 64, loss: str = "linear", f_scale: float = 1.0):
+    """Global bundle adjustment of all cameras and points (``sfmhip_ba_global_robust``).
 
     cam (C,6) = rvec, t (world -> camera); K (3,3) or (C,3,3), held fixed; X (N,3);
     observation m says camera obs_cam[m] saw point obs_pt[m] at pts2d[m], in any
@@ -394,8 +444,19 @@ def bundle_adjust(cam, K, X, obs_cam, obs_pt, pts2d, cam_fixed=None, gtol: float
     ``cost0``, ``cost``, ``status`` (1 gtol, 2 ftol, 0 max_iter, 3 damping overflow,
     -1 malformed observation list, -2 a point behind a camera at the start; for
     the negative ones cam and X are the inputs), ``nit`` (linearisations),
-    ``n_accept`` and ``n_cg``."""
+    ``n_accept`` and ``n_cg``; ``residual`` (M,), the final unweighted |r| of every
+    observation in pixels, in the caller's order (NaN for a negative status), and
+    ``weight`` (M,), the loss's weight at that residual.
+
+    ``loss``: "linear" (plain least squares), "huber", "soft_l1" or "cauchy", with the
+    scale ``f_scale`` > 0 in pixels.  The loss is applied per observation, to the
+    2-vector of its residual, as Ceres does — not per scalar component as scipy's
+    ``least_squares`` does: z = |r|^2 / f_scale^2, cost = 0.5 f_scale^2 sum rho(z) with
+    scipy's rho, weights w = rho'(z) (plain IRLS, no second-order correction).
+    ``cost0`` and ``cost`` are that robust cost.  Cauchy with f_scale of 1-2 px
+    converges on gross outliers; Huber under IRLS creeps."""
     require_gpu()
+    code, f_scale = _ba_loss(loss, f_scale)
     d = _ba_global_inputs(cam, K, X, obs_cam, obs_pt, pts2d)
     C, N, M = d["C"], d["N"], d["M"]
     if cam_fixed is None:
@@ -405,8 +466,11 @@ def bundle_adjust(cam, K, X, obs_cam, obs_pt, pts2d, cam_fixed=None, gtol: float
     camt, Xt = d["cam"].clone(), d["X"].clone()
     cost = (ctypes.c_double * 2)()
     info = (ctypes.c_int32 * 4)()
-    call("sfmhip_ba_global", ptr(camt), ptr(d["K"]), ptr(Xt), ptr(d["obs_cam"]), ptr(d["obs_pt"]), ptr(d["pts2d"]),
-         ptr(d["pt_off"]), ptr(d["cam_perm"]), ptr(d["cam_off"]), ptr(fx), C, N, M, float(gtol), float(ftol),
-         float(eta), int(max_iter), int(max_cg), ctypes.addressof(cost), ctypes.addressof(info), stream_ptr())
-    return SimpleNamespace(cam=camt.cpu().numpy(), X=Xt.cpu().numpy(), cost0=cost[0], cost=cost[1],
-                           status=int(info[0]), nit=int(info[1]), n_accept=int(info[2]), n_cg=int(info[3]))
+    res2 = torch.full((M,), float("nan"), dtype=torch.float64, device=camt.device)
+    call("sfmhip_ba_global_robust", ptr(camt), ptr(d["K"]), ptr(Xt), ptr(d["obs_cam"]), ptr(d["obs_pt"]),
+         ptr(d["pts2d"]), ptr(d["pt_off"]), ptr(d["cam_perm"]), ptr(d["cam_off"]), ptr(fx), C, N, M, float(gtol),
+         float(ftol), float(eta), int(max_iter), int(max_cg), ctypes.addressof(cost), ctypes.addressof(info),
+         stream_ptr(), code, f_scale, ptr(res2))
+    return _BundleResult(cam=camt.cpu().numpy(), X=Xt.cpu().numpy(), cost0=cost[0], cost=cost[1],
+                         status=int(info[0]), nit=int(info[1]), n_accept=int(info[2]), n_cg=int(info[3]),
+                         loss=loss, f_scale=f_scale, _res2=res2, _order=d["order"])

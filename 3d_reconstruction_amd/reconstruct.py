@@ -101,7 +101,8 @@ def incremental_sfm(img_pairs, all_matches, all_points, all_colors, n_images: in
 
 
 def global_refine(cameras, all_point3ds, img_pairs, all_matches, all_points, focal: float = FOCAL,
-                  gate_px: float = 4.0, fixed=None, **solver):
+                  gate_px: float = 4.0, fixed=None, loss: str = "linear", f_scale: float = 1.0, reject_px=None,
+                  polish: bool = False, **solver):
     """Global bundle adjustment of an :func:`incremental_sfm` result, in place
     (geometry.bundle_adjust; not part of the reference, whose loop only adjusts
     camera j and the new points of each pair).
@@ -120,8 +121,24 @@ def global_refine(cameras, all_point3ds, img_pairs, all_matches, all_points, foc
     ``all_point3ds[0]`` unless the solver reports an input error.  Returns
     (result, n_obs): bundle_adjust's result object, with ``n_candidates`` (before
     the gate) and the gated list ``obs_cam``, ``obs_track``, ``pts2d`` added, and
-    the number of observations adjusted."""
+    the number of observations adjusted.
+
+    With a robust ``loss`` ("huber", "soft_l1", "cauchy"; scale ``f_scale`` in pixels, see
+    bundle_adjust) the gate no longer has to separate right from wrong matches: ``gate_px``
+    may be wide or ``np.inf``, candidates with a non-positive depth under the incoming
+    reconstruction are dropped as well (one of them would end the solve with status -2), and
+    after the solve an observation is an inlier iff its final residual is at most
+    ``reject_px`` (default: ``gate_px`` if finite, else 4.0).  ``polish=True`` then runs a
+    second, linear bundle_adjust on the inliers of the tracks that keep at least two of them,
+    from the robust result.  Tracks with fewer than two inliers are set to ``None`` in
+    ``all_point3ds[0]`` and ``all_point3ds[1]``.  The result (of the polish when there is
+    one) gains ``inlier`` (bool, over the gated list) and ``robust`` (the first solve's
+    result when polished, else ``None``; the polish's own ``residual`` covers only the
+    observations it used)."""
     from .geometry import _residual, bundle_adjust
+    robust = loss != "linear"
+    if not robust and (polish or reject_px is not None):
+        raise ValueError("reject_px and polish need a robust loss")
     K = np.array([[focal, 0, 0], [0, focal, 0], [0, 0, 1.0]])
     have = np.array([p is not None for p in all_point3ds[0]])
     cand = []
@@ -144,6 +161,9 @@ def global_refine(cameras, all_point3ds, img_pairs, all_matches, all_points, foc
         cam6 = np.concatenate([rvec[c], np.asarray(cameras[c], np.float64)[:3, 3]])
         r = _residual(cam6, K.reshape(1, 9), Xc, uv[sel])
         keep[sel] = np.hypot(r[:, 0], r[:, 1]) <= gate_px
+        if robust:
+            P = np.asarray(cameras[c], np.float64)
+            keep[sel] &= Xc @ P[2, :3] + P[2, 3] > 0
     n_tr = len(have)
     keep &= (np.bincount(ot[keep], minlength=n_tr) >= 2)[ot]
     oc, ot, uv = oc[keep], ot[keep], uv[keep]
@@ -156,6 +176,28 @@ def global_refine(cameras, all_point3ds, img_pairs, all_matches, all_points, foc
         first = img_pairs[0][0] if len(img_pairs) and img_pairs[0][0] in cams else (cams[0] if len(cams) else None)
         fixed = () if first is None else (first,)
     cam_fixed = np.isin(cams, np.asarray(list(fixed), np.int64)).astype(np.uint8)
+    if robust:
+        first = bundle_adjust(cam6, K, X, cam_idx, tr_idx, uv, cam_fixed=cam_fixed, loss=loss, f_scale=f_scale, **solver)
+        res, inlier = first, np.zeros(len(oc), bool)
+        if first.status >= 0:
+            limit = reject_px if reject_px is not None else (gate_px if np.isfinite(gate_px) else 4.0)
+            inlier = first.residual <= limit
+            alive = np.bincount(tr_idx[inlier], minlength=len(trs)) >= 2
+            if polish:
+                use = inlier & alive[tr_idx]
+                res = bundle_adjust(first.cam, K, first.X, cam_idx[use], tr_idx[use], uv[use], cam_fixed=cam_fixed,
+                                    **solver)
+            for k, c in enumerate(cams):
+                if not cam_fixed[k]:
+                    cameras[c] = np.hstack((Rodrigues(res.cam[k, :3])[0], res.cam[k, 3:].reshape(3, 1)))
+            for k, t in enumerate(trs):
+                all_point3ds[0][t] = res.X[k] if alive[k] else None
+                if not alive[k]:
+                    all_point3ds[1][t] = None
+        res.inlier, res.robust = inlier, (first if res is not first else None)
+        res.n_candidates = len(cand)
+        res.obs_cam, res.obs_track, res.pts2d = oc, ot, uv
+        return res, len(oc)
     res = bundle_adjust(cam6, K, X, cam_idx, tr_idx, uv, cam_fixed=cam_fixed, **solver)
     if res.status >= 0:
         for k, c in enumerate(cams):

@@ -351,6 +351,31 @@ int sfmhip_ba_global(double* cam, const double* K, double* X, const int32_t* obs
                      const double* pts2d, const int64_t* pt_off, const int64_t* cam_perm, const int64_t* cam_off,
                      const uint8_t* cam_fixed, int C, int N, int64_t M, double gtol, double ftol, double eta,
                      int max_iter, int max_cg, double* cost, int32_t* info, void* stream);
+/* Robust loss (plain IRLS; DESIGN.md K3''' "Robust loss", tests/ba_robust_ref.py).  loss: 0 linear,
+ * 1 huber, 2 soft_l1, 3 cauchy; f_scale > 0 in pixels.  The loss acts on the 2-vector of an
+ * observation (as Ceres does, not per scalar component as scipy's least_squares does):
+ * z = |r|^2 / f_scale^2, cost = 0.5 f_scale^2 sum rho(z) with scipy's rho (huber: z if z <= 1, else
+ * 2 sqrt z - 1; soft_l1: 2 (sqrt(1 + z) - 1); cauchy: log1p z), weight w = rho'(z).  The
+ * linearisation stores sqrt(w) r, sqrt(w) Jc, sqrt(w) Jp in place of r, Jc, Jp, so blocks, gradient,
+ * damping, CG, back-substitution and the step rule are the robust Gauss-Newton ones unchanged; no
+ * second-order correction.  loss = 0 runs exactly what the two entries above run (they forward here).
+ * sfmhip_ba_global_linearize_robust: as sfmhip_ba_global_linearize, the arrays weighted, *cost the
+ * robust cost, weight [M] = w per sorted observation (1 for loss 0).
+ * sfmhip_ba_global_robust: as sfmhip_ba_global, cost[2] the robust cost; obs_res2 [M] (device,
+ * nullable) receives the final UNWEIGHTED |r|^2 of every sorted observation (not written for
+ * status -1 / -2).  An unknown loss code, or f_scale not > 0 or not finite: SFMHIP_E_ARG, checked
+ * before anything else.  */
+int sfmhip_ba_global_linearize_robust(const double* cam, const double* K, const double* X, const int32_t* obs_cam,
+                                      const int32_t* obs_pt, const double* pts2d, const int64_t* pt_off,
+                                      const int64_t* cam_perm, const int64_t* cam_off, int C, int N, int64_t M,
+                                      double* r, double* Jc, double* Jp, double* U, double* g_c, double* V,
+                                      double* g_p, double* cost, void* stream, int loss, double f_scale,
+                                      double* weight);
+int sfmhip_ba_global_robust(double* cam, const double* K, double* X, const int32_t* obs_cam, const int32_t* obs_pt,
+                            const double* pts2d, const int64_t* pt_off, const int64_t* cam_perm,
+                            const int64_t* cam_off, const uint8_t* cam_fixed, int C, int N, int64_t M, double gtol,
+                            double ftol, double eta, int max_iter, int max_cg, double* cost, int32_t* info,
+                            void* stream, int loss, double f_scale, double* obs_res2);
 
 /* ---- V1: voxel_traversal (voxel_travesal.py:1-73), quirks included -------
  * rays [N][8] f32 = o(3), d(3), near, far.  Pass 1 counts per-ray steps

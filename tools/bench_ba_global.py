@@ -10,6 +10,10 @@ that return at once (measured by shrinking max_cg to a value that still gives th
 iterations, bit for bit).
 
     python tools/bench_ba_global.py [--scipy-nfev 10] [--cams 257 --points 100000 --vis 0.03]
+    python tools/bench_ba_global.py --loss cauchy --f-scale 1 --outliers 0.05 --ftol 1e-8
+
+--loss / --f-scale choose the robust loss of bundle_adjust (default: linear); --outliers displaces
+that fraction of the observations by 20-100 px (the generator of tests/test_gpu_ba_robust.py).
 """
 import argparse
 import importlib
@@ -32,10 +36,22 @@ ap.add_argument("--vis", type=float, default=0.03)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--warmup", type=int, default=1)
 ap.add_argument("--gtol", type=float, default=1e-6)
+ap.add_argument("--ftol", type=float, default=1e-10)
+ap.add_argument("--loss", default="linear", choices=["linear", "huber", "soft_l1", "cauchy"])
+ap.add_argument("--f-scale", type=float, default=1.0)
+ap.add_argument("--outliers", type=float, default=0.0, help="fraction of observations displaced by 20-100 px")
 ap.add_argument("--scipy-nfev", type=int, default=0, help="0 skips the scipy arm")
 a = ap.parse_args()
 
 s = syn.ba_global_scene(C=a.cams, N=a.points, vis=a.vis, seed=31)
+n_out = 0
+if a.outliers > 0:
+    rng = np.random.default_rng(31 + 1000)
+    bad = rng.random(len(s["obs_cam"])) < a.outliers
+    n_out = int(bad.sum())
+    s["pts2d"][bad] += rng.uniform(20.0, 100.0, (n_out, 2)) * rng.choice([-1.0, 1.0], (n_out, 2))
+# the linear loss goes through the default arguments, as every caller before the robust loss did
+loss_kw = {} if a.loss == "linear" else dict(loss=a.loss, f_scale=a.f_scale)
 args = (s["cam"], s["K"], s["X"], s["obs_cam"], s["obs_pt"], s["pts2d"], s["cam_fixed"])
 M = len(s["obs_cam"])
 
@@ -45,7 +61,7 @@ def timed(max_cg, reps):
     for _ in range(reps):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        res = sfm.bundle_adjust(*args, gtol=a.gtol, max_cg=max_cg)
+        res = sfm.bundle_adjust(*args, gtol=a.gtol, ftol=a.ftol, max_cg=max_cg, **loss_kw)
         ts.append(time.perf_counter() - t0)
     return float(np.median(ts)) * 1e3, res
 
@@ -58,7 +74,7 @@ for _ in range(3):
 host_ms = (time.perf_counter() - t0) / 3 * 1e3
 # launches: a trial step = damp + 2 (right-hand side) + CG init + 3 per CG slot + back-substitution
 # + trial + 2 (trial cost) + step + accept; a linearisation = 5 + the gate
-out = dict(C=a.cams, N=a.points, M=M, ms_per_solve=round(ms, 2), host_structure_ms=round(host_ms, 2), status=res.status,
+out = dict(C=a.cams, N=a.points, M=M, loss=a.loss, f_scale=a.f_scale, outliers=n_out, ms_per_solve=round(ms, 2), host_structure_ms=round(host_ms, 2), status=res.status,
            linearisations=res.nit, accepted=res.n_accept, cg_iterations=res.n_cg, cost0=res.cost0, cost=res.cost,
            launches_per_trial=10 + 3 * 64, launches_per_linearisation=6)
 for k in (8, 12, 16, 24, 32, 48):
