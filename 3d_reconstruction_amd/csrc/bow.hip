@@ -1,7 +1,7 @@
 // bow.hip — BoW retrieval support: per-image visual-word
 // histograms (matching.py:30-35) and the k-means centroid update of
 // scipy.cluster.vq.kmeans (bow.py:23 -> scipy _vq.update_cluster_means).
-// Word assignment itself is sfmhip_vq (match.hip).
+// Word assignment itself is sfmhip_vq (vq.hip).
 #include "common.h"
 #include <climits>
 

@@ -42,6 +42,15 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 
 inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// Compute units of the current device (256 when the runtime does not say); asked at every call.
+inline int cu_count() {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+        return 256;
+    return n;
+}
+
 // Stream-ordered scratch from a library-owned memory pool per device (lib.hip):
 // freed scratch (up to 1 GiB) stays mapped between calls instead of going back
 // to the driver at every synchronisation (C5 TSDF: 2.32 -> 2.14 ms per call;

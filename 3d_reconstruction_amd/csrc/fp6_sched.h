@@ -1,4 +1,4 @@
-// fp6_sched.h — the instruction order of match_fp6_kernel's block loop (match.hip), shared with the
+// fp6_sched.h — the instruction order of match_fp6_kernel's block loop (match_fp6.hip), shared with the
 // registers-only probe tools/mfma_mx_peak.hip so that the probe times the order the kernel runs.
 #pragma once
 

@@ -1304,14 +1304,8 @@ static int tsdf_run(float* T, float* Wt, int D, int H, int W, int z0, int z1, co
     const int64_t main_slots = (int64_t)sm.per * kNumXcd;
     SFMHIP_REQUIRE(main_slots < INT_MAX / 2, "sfmhip_tsdf_integrate: grid too large");
     const Knobs kn = knobs();
-    int ncu = 256;
-    {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-            ncu = 256;
-        (void)hipGetLastError();
-    }
+    const int ncu = cu_count();
+    (void)hipGetLastError();
     const double rounds = (double)nsub / (ncu * 32.0);   // 8 waves per SIMD
     const bool latency_mode = kn.tsdf_latency >= 0 ? kn.tsdf_latency != 0 : rounds < kTsdfLatencyRounds;
     // a thin slab (fewer than kTsdfDeepRounds rounds of resident fusion waves: a z-slab of an N >= 4

@@ -1,0 +1,559 @@
+// vq.hip — M2 scipy-compatible vq (sfmhip_vq): every observation's nearest codeword and its distance.
+//
+// Reference boundary: scipy.cluster.vq.vq at matching.py:27.  Semantics: SURVEY.md §8a M2, pinned by
+// oracle/match.py.  Three forms (DESIGN.md "M2"): d = 128 with <= 256 codewords takes the f16-split
+// MFMA filter with an exact f64 decision (vq_f16s_kernel + vq_exact_kernel), other d <= 128 the
+// f64-MFMA GEMM form (vq_mfma_kernel), everything else the f64 difference form (vq_kernel).
+#include "common.h"
+#include <climits>
+#include <cstdlib>
+
+namespace sfmhip {
+
+// ---------------------------------------------------------------------------
+// vq: 16 lanes per observation (16 observations per workgroup); the code book
+// streams through LDS in chunks of 32 codewords (row stride padded by one f64
+// so the 16 codewords a wave reads at one k sit in distinct banks); each lane
+// accumulates 2 codewords of the chunk (sum of squared differences in k order,
+// one fused multiply-add per term: exact for integer-valued data, within
+// rounding of scipy's BLAS-form distance otherwise), then a 16-lane argmin
+// with lowest-index tie-break.
+constexpr int kVqObsPerBlock = 16;
+constexpr int kVqCodesPerChunk = 32;
+
+__global__ __launch_bounds__(256) void vq_kernel(const double* __restrict__ obs, int64_t n_obs,
+                                                 const double* __restrict__ code, int n_codes, int d,
+                                                 int32_t* __restrict__ codes, double* __restrict__ dist) {
+    extern __shared__ double smem[];
+    double* sobs = smem;                                   // [16][d]
+    double* scode = smem + kVqObsPerBlock * d;             // [64][d + 1]
+    const int ld = d + 1;
+    const int64_t o0 = (int64_t)blockIdx.x * kVqObsPerBlock;
+    for (int t = threadIdx.x; t < kVqObsPerBlock * d; t += blockDim.x) {
+        const int64_t o = o0 + t / d;
+        sobs[t] = (o < n_obs) ? obs[o * d + (t % d)] : 0.0;
+    }
+    const int lo = threadIdx.x >> 4, l16 = threadIdx.x & 15;
+    const double* x = sobs + lo * d;
+    double best = __builtin_inf();
+    int bidx = INT_MAX;
+    for (int c0 = 0; c0 < n_codes; c0 += kVqCodesPerChunk) {
+        const int nc = min(kVqCodesPerChunk, n_codes - c0);
+        __syncthreads();
+        for (int t = threadIdx.x; t < nc * d; t += blockDim.x) {
+            const int r = t / d;
+            scode[r * ld + (t - r * d)] = code[(size_t)(c0 + r) * d + (t - r * d)];
+        }
+        __syncthreads();
+        double acc[2] = {0.0, 0.0};
+        for (int k = 0; k < d; ++k) {
+            const double xv = x[k];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int r = l16 + 16 * j;
+                const double df = xv - scode[r * ld + k];
+                acc[j] = __builtin_fma(df, df, acc[j]);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {   // codewords ascend with j -> strict < keeps the lowest index
+            const int r = l16 + 16 * j;
+            if (r < nc && acc[j] < best) { best = acc[j]; bidx = c0 + r; }
+        }
+    }
+#pragma unroll
+    for (int off = 8; off >= 1; off >>= 1) {
+        const double ob = __shfl_xor(best, off, 16);
+        const int oi = __shfl_xor(bidx, off, 16);
+        if (ob < best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
+    }
+    const int64_t o = o0 + lo;
+    if (l16 == 0 && o < n_obs) {
+        codes[o] = bidx;
+        dist[o] = sqrt(best);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// vq on the f64 matrix cores: argmin_j of |c_j|^2 - 2 x.c_j (= d2 - |x|^2; the
+// GEMM form scipy's _vq uses, minus the row constant), with x.c from
+// v_mfma_f64_16x16x4_f64.  Exact for integer-valued data (every product and
+// partial sum is an integer below 2^53), so integer inputs give scipy's codes
+// and distances bit for bit; float inputs agree to rounding.
+//
+// Layout: one workgroup per CU (8 waves), persistent over 256-observation
+// tiles.  The code book passes through LDS in at most a few passes of <=144
+// codewords (row stride DP+4 f64, i.e. == 4 mod 32, so the 16 rows x 4 k of an
+// MFMA B fragment hit distinct bank pairs).  Each wave keeps the A fragments
+// of its 32 observations (2 row tiles x DP/4 f64 per lane) in registers for a
+// whole pass; every B fragment read from LDS feeds two MFMAs (two code blocks
+// per step, four accumulator chains, measured slower once the difference-form
+// epilogue raised register pressure: 1.37 vs 1.33 ms).  Each lane
+// tracks the best codeword among j == lane (mod 16) for its 4 C rows, then a
+// 16-lane (d2, index) argmin with lowest-index tie-break; passes merge through
+// the output arrays (strict <: later passes hold higher indices), and the
+// last pass writes the winner's distance recomputed in difference form,
+// sqrt(sum (x - c)^2): the GEMM form's cancellation noise would otherwise show
+// where x equals its codeword (kmeans singletons), which scipy reports as 0.
+typedef double v4d __attribute__((ext_vector_type(4)));
+constexpr int kVqmWaves = 8;
+constexpr int kVqmObsPerWave = 32;
+constexpr int kVqmTile = kVqmWaves * kVqmObsPerWave;   // 256 observations
+
+template <int DP, bool FULL>   // FULL: d == DP (no k padding)
+__global__ __launch_bounds__(kVqmWaves * 64) void vq_mfma_kernel(
+    const double* __restrict__ obs, int64_t n_obs, const double* __restrict__ code, int n_codes, int d,
+    int codes_per_pass, int32_t* __restrict__ codes, double* __restrict__ dist) {
+    constexpr int LD = DP + 4;
+    constexpr int KS = DP / 4;
+    extern __shared__ double smem[];
+    double* sc = smem;                                  // [codes_per_pass][LD]
+    double* sn = smem + (size_t)codes_per_pass * LD;    // [codes_per_pass] squared norms
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r16 = lane & 15, kq = lane >> 4;
+    const int64_t n_tiles = (n_obs + kVqmTile - 1) / kVqmTile;
+    for (int c0 = 0; c0 < n_codes; c0 += codes_per_pass) {
+        const int nc = min(codes_per_pass, n_codes - c0);
+        const int ncb = (nc + 15) >> 4;
+        const bool first = c0 == 0, last = c0 + codes_per_pass >= n_codes;
+        __syncthreads();
+        for (int t = threadIdx.x; t < ncb * 16 * DP; t += blockDim.x) {
+            const int r = t / DP, k = t - r * DP;
+            sc[r * LD + k] = (r < nc && (FULL || k < d)) ? code[(size_t)(c0 + r) * d + k] : 0.0;
+        }
+        __syncthreads();
+        for (int r = threadIdx.x; r < ncb * 16; r += blockDim.x) {
+            double s = 0.0;
+            for (int k = 0; k < DP; ++k) s = __builtin_fma(sc[r * LD + k], sc[r * LD + k], s);
+            sn[r] = r < nc ? s : __builtin_inf();    // padded codewords never win
+        }
+        __syncthreads();
+        for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+            const int64_t ob = t * kVqmTile + wave * kVqmObsPerWave;
+            double a[2][KS];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int64_t o = ob + 16 * h + r16;
+                const double* xp = obs + o * d;
+#pragma unroll
+                for (int s = 0; s < KS; ++s) {
+                    const int k = 4 * s + kq;
+                    a[h][s] = (o < n_obs && (FULL || k < d)) ? __builtin_nontemporal_load(xp + k) : 0.0;
+                }
+            }
+            double best[2][4];
+            int bj[2][4];
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) { best[h][g] = __builtin_inf(); bj[h][g] = INT_MAX; }
+            auto epilogue = [&](const v4d& acc0, const v4d& acc1, int j) {
+                const double cn = sn[j];
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const double d0 = cn - 2.0 * acc0[g];     // d2 - |x|^2: the row constant drops out
+                    const double d1 = cn - 2.0 * acc1[g];
+                    if (d0 < best[0][g]) { best[0][g] = d0; bj[0][g] = c0 + j; }
+                    if (d1 < best[1][g]) { best[1][g] = d1; bj[1][g] = c0 + j; }
+                }
+            };
+            for (int cb = 0; cb < ncb; ++cb) {
+                const int j = cb * 16 + r16;
+                const double* bp = sc + j * LD + kq;
+                v4d acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int s = 0; s < KS; ++s) {
+                    const double b = bp[4 * s];
+                    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[0][s], b, acc0, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[1][s], b, acc1, 0, 0, 0);
+                }
+                epilogue(acc0, acc1, j);
+            }
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                int win = 0;    // the winning codeword of row r16 (for the last pass's distance)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    double bv = best[h][g];
+                    int bi = bj[h][g];
+#pragma unroll
+                    for (int off = 8; off >= 1; off >>= 1) {
+                        const double ov = __shfl_xor(bv, off, 16);
+                        const int oi = __shfl_xor(bi, off, 16);
+                        if (ov < bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+                    }
+                    // all 16 lanes of the kq group now hold row kq + 4g's (d2, index)
+                    const int64_t o = ob + 16 * h + kq + 4 * g;
+                    if (!first && o < n_obs) {
+                        const double prev = dist[o];
+                        if (!(bv < prev)) { bv = prev; bi = codes[o]; }
+                    }
+                    if (!last && r16 == 0 && o < n_obs) {
+                        codes[o] = bi;
+                        dist[o] = bv;
+                    }
+                    const int w = __shfl(bi, (r16 & 3) * 16);        // row r16 = (r16 & 3) + 4 (r16 >> 2)
+                    if ((r16 >> 2) == g) win = w;
+                }
+                if (last) {
+                    // distance of the winner in difference form, sum (x - c)^2: exact 0 for x == c
+                    // (the GEMM form leaves cancellation noise there), otherwise within rounding
+                    const int64_t o = ob + 16 * h + r16;
+                    const double* cp = code + (size_t)win * d;
+                    double part = 0.0;
+#pragma unroll
+                    for (int s = 0; s < KS; ++s) {
+                        const int k = 4 * s + kq;
+                        const double df = a[h][s] - ((o < n_obs && (FULL || k < d)) ? cp[k] : 0.0);
+                        part = __builtin_fma(df, df, part);
+                    }
+                    part += __shfl_xor(part, 16);
+                    part += __shfl_xor(part, 32);
+                    if (kq == 0 && o < n_obs) {
+                        codes[o] = win;
+                        dist[o] = sqrt(part);
+                    }
+                }
+            }
+        }
+    }
+}
+
+
+// ---------------------------------------------------------------------------
+// vq, d = 128, <= 256 codewords: f32 filter + exact decision (default).
+// The f32 MFMA (2x the f64 matrix rate) computes the GEMM-form scores
+// s_j = fl32(|c_j|^2) - 2 (x_f . c_f)_f32 with a proven bound on |s_j - (|c_j|^2 - 2 x.c_j)|:
+//   input rounding of x and c (2^-24 each), the f32 accumulation of d products
+//   (gamma_d), the norm's rounding: eps = 1.01 ((2d + 5) 2^-24 |x| cmax + 2^-24 cmax^2).
+// An observation whose best two scores are more than 2 eps apart has a unique
+// exact argmin, the best one; its distance is then computed in f64 difference form
+// (sqrt(sum (x - c)^2)).  The others (near-ties, exact ties) go to a list that
+// vq_exact_kernel settles in f64 difference form over every codeword (lowest index
+// on ties) — on integer data every value involved is exact, so codes and distances
+// are scipy's bit for bit; on floats the decided argmins are the exact ones.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+// Absolute part of the f32 filter's error bound: an input, product or norm that
+// lands in (or is flushed from) the f32 subnormal range carries an absolute
+// error up to 2^-126 times the other factor, whatever the relative bound says
+// (data scaled to ~1e-21).  Per product <= 2^-126 (|c_k| + |x_k| + 1); summed
+// over DP products, times 2 in the score, plus the norm:
+// <= 2^-126 (2 sqrt(DP) (cmax + |x|) + 2 DP + 4).  Scores closer than that go
+// to the exact f64 pass.
+__device__ __forceinline__ double vq_eps_abs(int DP, double xn, double cmax) {
+    return 0x1p-126 * (2.0 * sqrt((double)DP) * (cmax + xn) + 2.0 * DP + 4.0) * 1.01;
+}
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+constexpr int kVqhWaves = 8;
+__device__ __forceinline__ double vq_eps16(int DP, double xn, double cmax) {
+    const double u = 0x1p-24;
+    return 1.01 * (2.0 * xn * cmax * (0x1.8p-21 + 2.02 * DP * u + 4.0 * u) + 4.0 * u * cmax * cmax +
+                   0x1p-24 * sqrt((double)DP) * (xn + cmax) + 2.0 * DP * 0x1p-48) +
+           vq_eps_abs(DP, xn, cmax);
+}
+// k of register j (< 16), half e, for lane group q: pair 8 (j & 7) + 2q + (j >> 3)
+__device__ __forceinline__ int vqh_k(int j, int e, int q) { return 16 * (j & 7) + 4 * q + 2 * (j >> 3) + e; }
+// lanes l and l ^ 8 of each 16-lane row swap a value (row_ror:8)
+__device__ __forceinline__ double vqh_xor8(double v) {
+    const int lo = __builtin_amdgcn_mov_dpp((int)__double2loint(v), 0x128, 0xF, 0xF, false);
+    const int hi = __builtin_amdgcn_mov_dpp((int)__double2hiint(v), 0x128, 0xF, 0xF, false);
+    return __hiloint2double(hi, lo);
+}
+__global__ __launch_bounds__(kVqhWaves * 64) void vq_f16s_kernel(const double* __restrict__ obs, int64_t n_obs,
+                                                                  const double* __restrict__ code, int n_codes,
+                                                                  int32_t* __restrict__ codes,
+                                                                  double* __restrict__ dist,
+                                                                  unsigned* __restrict__ amb,
+                                                                  unsigned* __restrict__ namb) {
+    constexpr int DP = 128, KB = 4, KS = 32;
+    extern __shared__ f32x4 smh[];
+    const int ncb = (n_codes + 15) >> 4;           // codeword blocks of 16
+    const int ncp = (ncb + 1) & ~1;                // LDS blocks (even count)
+    f16x8* sc = reinterpret_cast<f16x8*>(smh);     // [ncp][KB][2 (hi, lo)][64]
+    float* sn = reinterpret_cast<float*>(smh + ncp * KB * 2 * 64);   // [ncp * 16] squared norms
+    __shared__ unsigned s_cmax, s_big;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int r16 = lane & 15, kq = lane >> 4;
+    const bool b3 = (lane >> 3) & 1;
+    if (threadIdx.x == 0) { s_cmax = 0u; s_big = 0u; }
+    __syncthreads();
+    for (int t = threadIdx.x; t < ncp * KB * 64; t += blockDim.x) {
+        const int ln = t & 63, kb = (t >> 6) % KB, cb = t / (KB * 64);
+        const int j = cb * 16 + (ln & 15);
+        f16x8 hi, lo;
+        bool big = false;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {   // fragment element e of k-block kb = register 4 kb + e / 2, half e % 2
+            const double v = j < n_codes ? code[(size_t)j * DP + vqh_k(4 * kb + (e >> 1), e & 1, ln >> 4)] : 0.0;
+            big |= !(fabs(v) < 32768.0);
+            const _Float16 h = (_Float16)(float)v;
+            hi[e] = h;
+            lo[e] = (_Float16)(float)(v - (double)h);
+        }
+        if (big) s_big = 1u;
+        sc[((cb * KB + kb) * 2 + 0) * 64 + ln] = hi;
+        sc[((cb * KB + kb) * 2 + 1) * 64 + ln] = lo;
+    }
+    for (int r = threadIdx.x; r < ncp * 16; r += blockDim.x) {
+        double q = 0.0;
+        if (r < n_codes)
+            for (int k = 0; k < DP; ++k) q = __builtin_fma(code[(size_t)r * DP + k], code[(size_t)r * DP + k], q);
+        sn[r] = r < n_codes ? (float)q : __builtin_inff();   // padded codewords never win
+        if (r < n_codes) atomicMax(&s_cmax, __float_as_uint((float)sqrt(q) * 1.001f));
+    }
+    __syncthreads();
+    const double cmax = (double)__uint_as_float(s_cmax);
+    const bool book_big = s_big != 0u;
+    const int64_t n_units = (n_obs + 15) >> 4;
+    const int64_t ustep = (int64_t)gridDim.x * kVqhWaves;
+    f64x2 nx[KS / 2];   // the next unit's observations (load order), in flight while this unit computes
+    auto fetch = [&](int64_t un) {
+#pragma unroll
+        for (int j = 0; j < KS / 2; ++j) {   // rows (l & 7) + 8 (j >> 3), 128 B each
+            const f64x2* xp = reinterpret_cast<const f64x2*>(
+                                  obs + min(un * 16 + (lane & 7) + 8 * (j >> 3), n_obs - 1) * DP) +
+                              8 * (j & 7) + 2 * kq + b3;
+            nx[j] = __builtin_nontemporal_load(xp);
+        }
+    };
+    fetch(min((int64_t)blockIdx.x * kVqhWaves + wave, n_units - 1));
+    for (int64_t un = (int64_t)blockIdx.x * kVqhWaves + wave; un < n_units; un += ustep) {
+        const int64_t o = un * 16 + r16;
+        double x[KS];   // x[2 j + e] = row r16, k = vqh_k(j, e, kq) (fragment b, element i: x[8 b + i])
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {   // load order -> row order: swap registers m / 8 + m across lanes l, l ^ 8
+            const f64x2 a0 = nx[m], a1 = nx[8 + m];
+            const double s0 = vqh_xor8(b3 ? a0.x : a1.x), s1 = vqh_xor8(b3 ? a0.y : a1.y);
+            x[2 * m] = b3 ? s0 : a0.x;
+            x[2 * m + 1] = b3 ? s1 : a0.y;
+            x[16 + 2 * m] = b3 ? a1.x : s0;
+            x[16 + 2 * m + 1] = b3 ? a1.y : s1;
+        }
+        fetch(min(un + ustep, n_units - 1));
+        double xn = 0.0;
+        bool big = book_big;
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            xn = __builtin_fma(x[s], x[s], xn);
+            big |= !(fabs(x[s]) < 32768.0);
+        }
+        xn += __shfl_xor(xn, 16);
+        xn += __shfl_xor(xn, 32);   // |x|^2 of row r16, in every lane group
+        f16x8 ah[KB], al[KB];
+#pragma unroll
+        for (int b = 0; b < KB; ++b)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const _Float16 h = (_Float16)(float)x[8 * b + e];
+                ah[b][e] = h;
+                al[b][e] = (_Float16)(float)(x[8 * b + e] - (double)h);
+            }
+        float b1[4], b2[4];
+        int i1[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) { b1[g] = b2[g] = __builtin_inff(); i1[g] = INT_MAX; }
+        auto take = [&](int g, float dd, int j) {   // branch-free top-2 (selects)
+            const bool l = dd < b1[g];
+            b2[g] = l ? b1[g] : fminf(dd, b2[g]);
+            i1[g] = l ? j : i1[g];
+            b1[g] = l ? dd : b1[g];
+        };
+        for (int cb = 0; cb < ncb; cb += 2) {   // two blocks per pass (the odd last one's partner is padding)
+            const f16x8* bp = sc + cb * KB * 2 * 64 + lane;
+            f32x4 m0 = {0.f, 0.f, 0.f, 0.f}, m1 = m0, c0 = m0, c1 = m0;   // main / correction accumulators
+#pragma unroll
+            for (int b = 0; b < KB; ++b) {
+                const f16x8 c0h = bp[(b * 2 + 0) * 64], c0l = bp[(b * 2 + 1) * 64];
+                const f16x8 c1h = bp[((KB + b) * 2 + 0) * 64], c1l = bp[((KB + b) * 2 + 1) * 64];
+                m0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[b], c0h, m0, 0, 0, 0);
+                m1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[b], c1h, m1, 0, 0, 0);
+                c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[b], c0l, c0, 0, 0, 0);
+                c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[b], c1l, c1, 0, 0, 0);
+                c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[b], c0h, c0, 0, 0, 0);
+                c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[b], c1h, c1, 0, 0, 0);
+            }
+            const int j0 = cb * 16 + r16;
+            const float cn0 = sn[j0], cn1 = sn[j0 + 16];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {   // C row 4 kq + g (observation), columns j0, j0 + 16
+                take(g, cn0 - 2.f * (m0[g] + c0[g]), j0);
+                take(g, cn1 - 2.f * (m1[g] + c1[g]), j0 + 16);
+            }
+        }
+        // the filter's bound for row r16 (every lane group holds |x|^2 of its row r16): formed once
+        // per lane, then fetched for the lane's four C rows 4 kq + g
+        const double eps_row = vq_eps16(DP, sqrt(xn), cmax);
+        int win[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            float v1 = b1[g], v2 = b2[g];
+            int x1 = i1[g];
+#pragma unroll
+            for (int off = 8; off >= 1; off >>= 1) {   // top-2 over the 16 codeword lanes
+                const float o1 = __shfl_xor(v1, off, 16), o2 = __shfl_xor(v2, off, 16);
+                const int ox = __shfl_xor(x1, off, 16);
+                const bool t = o1 < v1 || (o1 == v1 && ox < x1);
+                v2 = t ? fminf(v1, o2) : fminf(o1, v2);
+                v1 = t ? o1 : v1;
+                x1 = t ? ox : x1;
+            }
+            const double eps = __shfl(eps_row, 4 * kq + g);   // lane 4kq+g: row 4kq+g's bound
+            win[g] = ((double)v2 - (double)v1 > 2.0 * eps) ? x1 : -1;
+        }
+        int w = -1;   // row r16's verdict: group r16 >> 2, entry r16 & 3
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int t = __shfl(win[g], (r16 >> 2) << 4);
+            if ((r16 & 3) == g) w = t;
+        }
+        // an out-of-range input anywhere in the row (any lane group) decides nothing
+        const bool rbig = __shfl_xor((int)big, 16) | __shfl_xor((int)big, 32) | __shfl_xor((int)big, 48) | big;
+        if (rbig) w = -1;
+        const f64x2* cp = reinterpret_cast<const f64x2*>(code + (size_t)max(w, 0) * DP) + 2 * kq;
+        double part = 0.0;
+#pragma unroll
+        for (int b = 0; b < KB; ++b) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const int j = 4 * b + t;   // register j: pair 8 (j & 7) + 2 kq + (j >> 3)
+                const f64x2 c = cp[8 * (j & 7) + (j >> 3)];
+                const double d0 = x[2 * j] - c.x, d1 = x[2 * j + 1] - c.y;
+                part = __builtin_fma(d0, d0, part);
+                part = __builtin_fma(d1, d1, part);
+            }
+            __builtin_amdgcn_sched_barrier(0);   // 4 codeword loads in flight (VGPRs)
+        }
+        part += __shfl_xor(part, 16);
+        part += __shfl_xor(part, 32);
+        if (kq == 0 && o < n_obs) {
+            if (w >= 0) {
+                codes[o] = w;
+                dist[o] = sqrt(part);
+            } else {
+                amb[atomicAdd(namb, 1u)] = (unsigned)o;
+            }
+        }
+    }
+}
+
+// The observations vq_f16s_kernel could not decide: one wave each, every codeword
+// in f64 difference form, lowest index on ties.
+__global__ __launch_bounds__(256) void vq_exact_kernel(const double* __restrict__ obs, const double* __restrict__ code,
+                                                       int n_codes, int d, const unsigned* __restrict__ amb,
+                                                       const unsigned* __restrict__ namb, int32_t* __restrict__ codes,
+                                                       double* __restrict__ dist) {
+    // one wave per listed observation: four 16-lane groups take four codewords at a time, lane
+    // k16 of a group the dims 8 k16 .. 8 k16 + 7 of each 128-dim chunk (a codeword row is read as
+    // contiguous 1 KB pieces); partial sums of squared differences, then a 16-lane sum.  On
+    // integer data every partial sum is exact, so any order gives the same q.
+    const int lane = threadIdx.x & 63, cg = lane >> 4, k16 = lane & 15;
+    const unsigned n = *namb;
+    for (unsigned e = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); e < n; e += gridDim.x * 4) {
+        const int64_t o = amb[e];
+        const double* xp = obs + o * d;
+        double best = __builtin_inf();
+        int bi = INT_MAX;
+        for (int j0 = 0; j0 < n_codes; j0 += 4) {
+            const int j = j0 + cg;
+            const double* cp = code + (size_t)min(j, n_codes - 1) * d;
+            double q = 0.0;
+            for (int k0 = 8 * k16; k0 < d; k0 += 128) {
+#pragma unroll
+                for (int t = 0; t < 8; ++t) {
+                    const int k = k0 + t;
+                    if (k < d) {
+                        const double df = xp[k] - cp[k];
+                        q = __builtin_fma(df, df, q);
+                    }
+                }
+            }
+#pragma unroll
+            for (int off = 8; off >= 1; off >>= 1) q += __shfl_xor(q, off, 16);
+            if (j < n_codes && q < best) { best = q; bi = j; }   // j increasing per group: the lowest kept
+        }
+#pragma unroll
+        for (int off = 32; off >= 16; off >>= 1) {   // across the four groups, lowest index on ties
+            const double ob = __shfl_xor(best, off);
+            const int oi = __shfl_xor(bi, off);
+            if (ob < best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+        }
+        if (lane == 0) {
+            codes[o] = bi;
+            dist[o] = sqrt(best);
+        }
+    }
+}
+
+}  // namespace sfmhip
+
+using namespace sfmhip;
+
+extern "C" int sfmhip_vq(const double* obs, int64_t n_obs, const double* code_book, int n_codes, int d,
+                         int32_t* codes, double* dist, void* stream) {
+    SFMHIP_REQUIRE(n_obs >= 0 && n_codes > 0 && d > 0 && d <= 256, "sfmhip_vq: bad shape (d <= 256)");
+    if (n_obs == 0) return SFMHIP_OK;
+    SFMHIP_REQUIRE(obs && code_book && codes && dist, "sfmhip_vq: null pointer");
+    // d = 128, <= 256 codewords (matching.py:27's 200-word codebook): the f16-split MFMA
+    // filter + exact f64 decision (vq_f16s_kernel + vq_exact_kernel); other shapes: the
+    // f64-MFMA GEMM-form kernel (d <= 128) or the f64 difference-form kernel.  The f32
+    // filter kernels (LDS-staged and register-resident) measured slower.
+    if (d == 128 && n_codes <= 256) {
+        const int ncp = ceil_div(n_codes, 32) * 2;
+        const size_t shm = (size_t)ncp * 4 * 2 * 64 * 16 + (size_t)ncp * 16 * sizeof(float);
+        hipStream_t s = as_stream(stream);
+        unsigned* amb = nullptr;
+        if (scratch_alloc((void**)&amb, (size_t)(n_obs + 1) * sizeof(unsigned), s) == hipSuccess &&
+            n_obs < ((int64_t)1 << 32) - 1) {
+            unsigned* namb = amb + n_obs;
+            (void)hipMemsetAsync(namb, 0, sizeof(unsigned), s);
+            const int n_cu = cu_count();
+            const int64_t n_wg = ((n_obs + 15) / 16 + kVqhWaves - 1) / kVqhWaves;
+            auto kern = vq_f16s_kernel;
+            (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+            hipLaunchKernelGGL(kern, dim3((unsigned)std::min<int64_t>(n_wg, n_cu)), dim3(kVqhWaves * 64), shm, s, obs,
+                               n_obs, code_book, n_codes, codes, dist, amb, namb);
+            int rc = check_launch("vq_f16s_kernel");
+            if (rc == SFMHIP_OK) {
+                hipLaunchKernelGGL(vq_exact_kernel, dim3(1024), dim3(256), 0, s, obs, code_book, n_codes, 128, amb,
+                                   namb, codes, dist);
+                rc = check_launch("vq_exact_kernel");
+            }
+            scratch_free(amb, s);
+            return rc;
+        }
+        (void)hipGetLastError();   // no scratch: the f64 kernels below
+    }
+    const int dp = d <= 32 ? 32 : d <= 64 ? 64 : d <= 128 ? 128 : 0;
+    if (dp) {
+        const int ld = dp + 4;
+        const int max_cpp = std::min(144, (int)((150 * 1024 / 8) / (ld + 1)) / 16 * 16);
+        const int passes = ceil_div(n_codes, max_cpp);
+        const int cpp = ceil_div(ceil_div(n_codes, passes), 16) * 16;
+        const size_t shm = (size_t)cpp * (ld + 1) * sizeof(double);
+        const int n_cu = cu_count();
+        const int64_t n_tiles = (n_obs + kVqmTile - 1) / kVqmTile;
+        const int grid = (int)std::min<int64_t>(n_tiles, n_cu);
+        hipStream_t s = as_stream(stream);
+#define SFMHIP_LAUNCH_VQM(DP, FL)                                                                             \
+    do {                                                                                                  \
+        (void)hipFuncSetAttribute((const void*)vq_mfma_kernel<DP, FL>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                  (int)shm);                                                               \
+        hipLaunchKernelGGL((vq_mfma_kernel<DP, FL>), dim3(grid), dim3(kVqmWaves * 64), shm, s, obs, n_obs,      \
+                           code_book, n_codes, d, cpp, codes, dist);                                       \
+    } while (0)
+        if (dp == 32) SFMHIP_LAUNCH_VQM(32, false);
+        else if (dp == 64) SFMHIP_LAUNCH_VQM(64, false);
+        else if (d != 128) SFMHIP_LAUNCH_VQM(128, false);
+        else SFMHIP_LAUNCH_VQM(128, true);
+#undef SFMHIP_LAUNCH_VQM
+        return check_launch("vq_mfma_kernel");
+    }
+    const int64_t blocks = (n_obs + kVqObsPerBlock - 1) / kVqObsPerBlock;
+    SFMHIP_REQUIRE(blocks < INT_MAX, "sfmhip_vq: too many observations");
+    const size_t shm = (size_t)(kVqObsPerBlock * d + kVqCodesPerChunk * (d + 1)) * sizeof(double);
+    SFMHIP_REQUIRE(shm <= 160 * 1024, "sfmhip_vq: descriptor dim too large for the LDS tiles");
+    hipLaunchKernelGGL(vq_kernel, dim3((int)blocks), dim3(256), shm, as_stream(stream), obs, n_obs, code_book,
+                       n_codes, d, codes, dist);
+    return check_launch("vq_kernel");
+}

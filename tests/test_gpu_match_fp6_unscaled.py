@@ -128,6 +128,39 @@ def test_every_row_through_the_resolve(sfm, gpu, knob, kind, m, d):
         assert nres == sum(int(nk[a]) for a, _ in PAIRS)
 
 
+def _check_entries_without_key_values(sfm, gpu, kind, m, d):
+    x, nk, g, ref = _case(kind, m, d)
+    bank = _bank(sfm, x, nk)
+    pr = torch.from_numpy(PAIRS).to(gpu)
+    for dtype, entry in ((torch.int32, "sfmhip_match_pairs_exact_fp6"), (torch.int16, "sfmhip_match_pairs_exact_fp6_i16")):
+        want = torch.empty((len(PAIRS), m), dtype=dtype, device=gpu)
+        bank.match(PAIRS, ratio=0.75, out=want)                               # the _kv entry on the same bank
+        want_res = int(bank.last_resolved.item())
+        got = torch.full_like(want, 7)
+        nres = torch.full((1,), 7, dtype=torch.int32, device=gpu)
+        abi.call(entry, abi.ptr(bank.dense), abi.ptr(bank.g), abi.ptr(bank.gnorms), abi.ptr(bank.gkeys),
+                 abi.ptr(bank.x), abi.ptr(bank.gerow), abi.ptr(bank.geimg), abi.ptr(bank.n_kpts), bank.n_img,
+                 bank.m_pad, bank.d, abi.ptr(pr), len(PAIRS), 3, 4, abi.ptr(got), abi.ptr(nres), abi.stream_ptr())
+        torch.cuda.synchronize()
+        assert torch.equal(got, want), entry
+        assert np.array_equal(got.cpu().numpy().astype(np.int64), ref), entry
+        assert int(nres.item()) == want_res, entry
+
+
+@pytest.mark.parametrize("kind,m,d", CASES)
+def test_entries_without_key_values_give_the_kv_graph(sfm, gpu, kind, m, d):
+    """sfmhip_match_pairs_exact_fp6 / _fp6_i16 build h and hf in the call's own scratch: the same graph, row
+    for row the oracle's, and the same resolved-row count as the _kv entries on the bank's key values."""
+    _check_entries_without_key_values(sfm, gpu, kind, m, d)
+
+
+@pytest.mark.parametrize("kind,m,d", CASES)
+def test_entries_without_key_values_on_the_int8_kernel(sfm, gpu, knob, kind, m, d):
+    """SFMHIP_MATCH_FP6=0: the int8 value-only kernel on g, h built per call and no hf."""
+    knob("MATCH_FP6", 0)
+    _check_entries_without_key_values(sfm, gpu, kind, m, d)
+
+
 @pytest.mark.parametrize("m", [640, 128])
 def test_key_values_entry(sfm, gpu, m):
     """sfmhip_match_key_values against key_values_kernel's definition: h = keys >> 8 bit for bit, and

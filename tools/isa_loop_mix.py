@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Instruction order of a kernel's MFMA loop, read from the assembly `make asm-<name>` writes.
 
-  tools/isa_loop_mix.py 3d_reconstruction_amd/csrc/match.s match_fp6_kernelILi256Es
+  tools/isa_loop_mix.py 3d_reconstruction_amd/csrc/match_fp6.s match_fp6_kernelILi256Es
 
 The loop is the innermost backward branch whose body holds the most MFMAs (the block loop of the match
 kernels).  Printed: the body's opcodes as run lengths in program order, and

@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256, 2) void kern_i8(const int* __restrict__ seed, 
                         t2[t] = max(t2[t], m);
                     }
             } else if (EPI == 2) {
-                // the accumulators' first reader is plain C++ (match.hip: stale values through inline asm)
+                // the accumulators' first reader is plain C++ (match.hip, match_fp6.hip: stale values through inline asm)
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     if (jt == 0) rm[t] = INT_MIN;
@@ -190,7 +190,7 @@ __global__ __launch_bounds__(256, 2) void kern_mx(const int* __restrict__ seed, 
     out[blockIdx.x * blockDim.x + threadIdx.x] = t1[0] + t2[0] + t1[1] + t2[1] + t1[2] + t2[2] + t1[3] + t2[3];
 }
 
-// The FP6 match kernel's real shape (match.hip, match_fp6_kernel<256>): 8 chains per wave, two k-steps per
+// The FP6 match kernel's real shape (match_fp6.hip, match_fp6_kernel<256>): 8 chains per wave, two k-steps per
 // tile, 6-register operands, the f32 group-max epilogue with the per-range merge every 4th tile, unit
 // scale, 2 waves per SIMD.  PIPE 0: the tile's 16 MFMAs, then its 16 max3, then (every 4th tile) the 32
 // merge instructions, in the order the compiler chooses (clustered).  PIPE 1: the same instructions in the

@@ -1,5 +1,5 @@
 """Offline model (CPU, numpy): how many C3 rows would a block-scaled FP6 (e2m3) or FP4 (e2m1)
-MFMA pass decide under the exact-float certificate that the int8 pass uses (csrc/match.hip
+MFMA pass decide under the exact-float certificate that the int8 pass uses (csrc/match_dev.h
 certify: |x_a - x_b| within E = |delta_a| + E_img[b] of the quantised distance)?  The
 undecided rows would need the exact re-score, so the share decided bounds the use of the
 2x-rate MX formats.  Prints the decided shares of int8 (today), FP6, FP4.
