@@ -917,7 +917,9 @@ static Bounds make_bounds(const float* bmin, const float* bmax) {
 extern "C" int sfmhip_grid_sample(const float* grid, int C, int D, int H, int W, const float* bmin,
                                   const float* bmax, int mask_mode, const float* pts, int64_t P, float* out,
                                   void* stream) {
-    SFMHIP_REQUIRE(C > 0 && D > 1 && H > 1 && W > 1 && P >= 0, "sfmhip_grid_sample: bad shape");
+    // an axis of one voxel is legal, as in sfmhip_nerf_forward and ATen's grid_sampler_3d: its
+    // index is ((g + 1) / 2) * 0 = 0 and the +1 corner is out of range (skipped)
+    SFMHIP_REQUIRE(C > 0 && D > 0 && H > 0 && W > 0 && P >= 0, "sfmhip_grid_sample: bad shape");
     SFMHIP_REQUIRE(mask_mode == 0 || mask_mode == 1, "sfmhip_grid_sample: mask_mode must be 0 or 1");
     if (P == 0) return SFMHIP_OK;
     SFMHIP_REQUIRE(grid && bmin && bmax && pts && out, "sfmhip_grid_sample: null pointer");

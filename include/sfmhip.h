@@ -401,7 +401,8 @@ int sfmhip_voxel_traversal_rows(const float* buf, int32_t cap, const int32_t* n_
  * mask_mode 0: sdf.py  (inside iff bmin <= p <= bmax, normalise to [-1,1])
  * mask_mode 1: plenoxel (inside iff |p| < scale=bmax[0], p/scale clipped)
  * out [P][C] (zero outside).  F.grid_sample(align_corners=True, zeros)
- * arithmetic, x->W, y->H, z->D.  bmin/bmax are HOST float[3].               */
+ * arithmetic, x->W, y->H, z->D.  bmin/bmax are HOST float[3].  D, H, W >= 1,
+ * here and in sfmhip_nerf_forward: an axis of one voxel has index 0.       */
 int sfmhip_grid_sample(const float* grid, int C, int D, int H, int W,
                        const float* bmin, const float* bmax, int mask_mode,
                        const float* pts, int64_t P, float* out, void* stream);

@@ -307,8 +307,26 @@ def block_table(depth) -> np.ndarray:
     return out
 
 
+def _min754(a, b):
+    """IEEE 754-2019 minimum: NaN-propagating, -0 below +0 (np.minimum returns its second
+    operand when the two compare equal, so the sign of a zero would follow the operand order)."""
+    a, b = np.broadcast_arrays(np.asarray(a, F32), np.asarray(b, F32))
+    with np.errstate(invalid="ignore"):
+        return np.where(a == b, np.where(np.signbit(a), a, b), np.minimum(a, b)).astype(F32)
+
+
+def _max754(a, b):
+    """IEEE 754-2019 maximum: NaN-propagating, +0 above -0."""
+    a, b = np.broadcast_arrays(np.asarray(a, F32), np.asarray(b, F32))
+    with np.errstate(invalid="ignore"):
+        return np.where(a == b, np.where(np.signbit(a), b, a), np.maximum(a, b)).astype(F32)
+
+
 def ray_aabb(rays_o, rays_d, bmin, bmax):
-    """GradientBasedSampler.ray_aabb_intersection (sdf.py:154-165), f32, NaN-propagating."""
+    """GradientBasedSampler.ray_aabb_intersection (sdf.py:154-165), f32, NaN-propagating.
+    Where a minimum or maximum meets -0 and +0 (a direction component of +-inf), torch's CPU
+    kernels return either, depending on whether the element falls in the vectorised body or the
+    scalar tail; here, as on the GPU, -0 orders below +0."""
     o = np.asarray(rays_o, F32).reshape(-1, 3)
     d = np.asarray(rays_d, F32).reshape(-1, 3)
     mn = np.asarray(bmin, F32).ravel()
@@ -317,9 +335,10 @@ def ray_aabb(rays_o, rays_d, bmin, bmax):
         inv = (F32(1.0) / d).astype(F32)
         t0 = ((mn - o) * inv).astype(F32)
         t1 = ((mx - o) * inv).astype(F32)
-    tn = np.max(np.minimum(t0, t1), axis=-1)
-    tf = np.min(np.maximum(t0, t1), axis=-1)
-    tn = np.maximum(tn, F32(0))
+    lo, hi = _min754(t0, t1), _max754(t0, t1)
+    tn = _max754(_max754(lo[:, 0], lo[:, 1]), lo[:, 2])
+    tf = _min754(_min754(hi[:, 0], hi[:, 1]), hi[:, 2])
+    tn = _max754(tn, F32(0))
     with np.errstate(invalid="ignore"):
         valid = tf > tn
     return tn.astype(F32), tf.astype(F32), valid
