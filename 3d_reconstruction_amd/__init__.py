@@ -17,7 +17,8 @@ from .geometry import (Rodrigues, ba_sparse, calculate_reprojection_error,  # no
                        convertPointsFromHomogeneous, fd_jacobian, projectPoints,
                        residual_jacobian_batched, triangulatePoints, triangulate_batched, ba_solve_batched,
                        least_squares_ba, ba_global_structure, ba_global_linearize, ba_global_schur_matvec,
-                       bundle_adjust, ba_loss_weight)
+                       bundle_adjust, ba_loss_weight, ba_calib_linearize, ba_calib_matvec, undistort_points,
+                       undistortPoints)
 from .voxel import (MASK_PLENOXEL, MASK_SDF, VoxelGrid, icp_normal_equations, icp_track, tsdf_block_table,  # noqa: F401,E501
                     tsdf_cull_stats, tsdf_integrate, tsdf_extract_surface, tsdf_integrate_colour, tsdf_layer_cost,
                     tsdf_layer_stats, tsdf_raycast, tsdf_track, voxel_traversal)

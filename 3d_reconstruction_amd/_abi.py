@@ -97,6 +97,10 @@ SIGNATURES = {
                                           _p, _p, _p, _i32, _f64, _p],
     "sfmhip_ba_global_robust": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _f64, _f64, _f64, _i32, _i32,
                                 _p, _p, _p, _i32, _f64, _p],
+    "sfmhip_ba_calib_linearize": [_p] * 12 + [_i32, _i32, _i32, _i64] + [_p] * 13 + [_i32, _f64, _p],
+    "sfmhip_ba_calib_matvec": [_p] * 15 + [_i32, _i32, _i32, _i64, _f64, _p, _p, _p],
+    "sfmhip_ba_calib": [_p] * 13 + [_i32, _i32, _i32, _i64, _f64, _f64, _f64, _i32, _i32, _p, _p, _p, _i32, _f64, _p],
+    "sfmhip_undistort_points": [_p, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _p, _p],
     "sfmhip_voxel_traversal_count": [_p, _i64, _f32, _i32, _p, _p],
     "sfmhip_voxel_traversal": [_p, _i64, _f32, _i32, _p, _p],
     "sfmhip_voxel_traversal_capped": [_p, _i64, _f32, _i32, _p, _p, _p],

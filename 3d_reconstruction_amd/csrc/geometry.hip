@@ -365,9 +365,42 @@ __global__ __launch_bounds__(kFdThreads) void fdjac_kernel(const double* __restr
     for (int64_t e = threadIdx.x; e < nv; e += kFdThreads) out[e] = sj[e];
 }
 
+// Inverse of the radial model u = fx (d xn) + cx, v = fy (d yn) + cy, d = 1 + k1 r2 + k2 r2^2: from
+// the distorted normalised point (xd, yd), kUndistortIters fixed-point steps xn <- xd / d(xn) from
+// xn = xd (no data-dependent exit: tests/ba_calib_ref.py restates it op for op), then the pixel
+// under the same K without distortion.  One lane per point.
+constexpr int kUndistortIters = 20;
+__global__ __launch_bounds__(256) void undistort_kernel(const double* __restrict__ src, int64_t n, double fx, double fy,
+                                                        double cx, double cy, double k1, double k2,
+                                                        double* __restrict__ dst) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double xd = (src[2 * i] - cx) / fx, yd = (src[2 * i + 1] - cy) / fy;
+    double xn = xd, yn = yd;
+    for (int it = 0; it < kUndistortIters; ++it) {
+        const double r2 = xn * xn + yn * yn;
+        const double d = (1.0 + k1 * r2) + k2 * (r2 * r2);
+        xn = xd / d;
+        yn = yd / d;
+    }
+    dst[2 * i] = xn * fx + cx;
+    dst[2 * i + 1] = yn * fy + cy;
+}
+
 }  // namespace sfmhip
 
 using namespace sfmhip;
+
+extern "C" int sfmhip_undistort_points(const double* src, int64_t n, double fx, double fy, double cx, double cy,
+                                       double k1, double k2, double* dst, void* stream) {
+    SFMHIP_REQUIRE(n >= 0, "sfmhip_undistort_points: negative n");
+    SFMHIP_REQUIRE(fx != 0.0 && fy != 0.0, "sfmhip_undistort_points: zero focal length");
+    if (n == 0) return SFMHIP_OK;
+    SFMHIP_REQUIRE(src && dst, "sfmhip_undistort_points: null pointer");
+    hipLaunchKernelGGL(undistort_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, as_stream(stream), src, n, fx, fy, cx,
+                       cy, k1, k2, dst);
+    return check_launch("undistort_kernel");
+}
 
 extern "C" int sfmhip_triangulate_dlt(const double* P, const int32_t* pair_of_obs, const double* x0,
                                       const double* x1, int64_t n, double* X4, void* stream) {

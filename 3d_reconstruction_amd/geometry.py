@@ -429,8 +429,148 @@ class _BundleResult(SimpleNamespace):
         return ba_loss_weight(self._e2(), self.loss, self.f_scale)
 
 
+# K3''' with intrinsics (ba_calib.hip): theta = (f, cx, cy, k1, k2) per intrinsics group
+_CALIB_PARTS = {"f": (0,), "pp": (1, 2), "k1": (3,), "k2": (4,)}
+
+
+def _calib_mask(refine_intrinsics) -> np.ndarray:
+    if isinstance(refine_intrinsics, str):
+        refine_intrinsics = (refine_intrinsics,)
+    mask = np.zeros(5, np.uint8)
+    for name in refine_intrinsics:
+        if name not in _CALIB_PARTS:
+            raise ValueError(f"refine_intrinsics must be a subset of {sorted(_CALIB_PARTS)}, got {name!r}")
+        mask[list(_CALIB_PARTS[name])] = 1
+    return mask
+
+
+def _calib_dist(dist) -> np.ndarray:
+    """(2,) / (G,2) = k1, k2, or a cv2 vector (k1, k2, p1, p2[, k3]) with p1 = p2 = k3 = 0 -> (1,2) / (G,2)."""
+    d = np.zeros((1, 2)) if dist is None else np.asarray(dist, np.float64)
+    if d.ndim == 2 and d.shape[1] == 2:
+        return np.ascontiguousarray(d)
+    d = d.ravel()
+    if d.size in (4, 5):
+        if np.any(d[2:] != 0):
+            raise NotImplementedError("only radial distortion (k1, k2) is modelled: p1, p2 and k3 must be 0")
+        d = d[:2]
+    if d.size != 2:
+        raise ValueError("dist must be (2,), (G, 2) or a cv2 distortion vector of 4 or 5 entries")
+    return np.ascontiguousarray(d.reshape(1, 2))
+
+
+def _calib_inputs(d: dict, dist, refine_intrinsics, cam_group) -> dict:
+    """Adds theta (G,5), asp (G,), cam_group (C,), mask (5,) device tensors and G to the inputs."""
+    C = d["C"]
+    K = d["K"].cpu().numpy()
+    mask = _calib_mask(refine_intrinsics)
+    dist = _calib_dist(dist)
+    grp = np.zeros(C, np.int64) if cam_group is None else np.asarray(cam_group).astype(np.int64).ravel()
+    if grp.shape != (C,):
+        raise ValueError("cam_group must have one entry per camera")
+    if C and grp.min() < 0:
+        raise ValueError("cam_group entries must not be negative")
+    G = max(int(grp.max()) + 1 if C else 1, len(dist) if len(dist) > 1 else 1)
+    if len(dist) == 1:
+        dist = np.repeat(dist, G, 0)
+    if len(dist) != G:
+        raise ValueError(f"dist has {len(dist)} rows for {G} intrinsics groups")
+    if C and (np.any(K[:, 0, 1] != 0) or np.any(K[:, 1, 0] != 0)):
+        raise ValueError("the camera matrices must have zero skew")
+    theta = np.zeros((G, 5))
+    theta[:, 0] = 1.0                                    # a group without cameras: never read
+    asp = np.ones(G)
+    for g in np.unique(grp):
+        Kg = K[grp == g]
+        if np.any(Kg != Kg[0]):
+            raise ValueError(f"the cameras of intrinsics group {g} must share one camera matrix")
+        theta[g, :3] = Kg[0, 0, 0], Kg[0, 0, 2], Kg[0, 1, 2]
+        asp[g] = Kg[0, 1, 1] / Kg[0, 0, 0]
+    theta[:, 3:] = dist
+    d.update(G=G, theta=dev(theta, torch.float64), asp=dev(asp, torch.float64),
+             cam_group=dev(grp.astype(np.int32), torch.int32), mask=dev(mask, torch.uint8))
+    return d
+
+
+def _calib_K(theta: np.ndarray, asp: np.ndarray, grp: np.ndarray) -> np.ndarray:
+    K = np.zeros((len(grp), 3, 3))
+    K[:, 0, 0] = theta[grp, 0]
+    K[:, 1, 1] = theta[grp, 0] * asp[grp]
+    K[:, 0, 2] = theta[grp, 1]
+    K[:, 1, 2] = theta[grp, 2]
+    K[:, 2, 2] = 1.0
+    return K
+
+
+def ba_calib_linearize(cam, K, X, obs_cam, obs_pt, pts2d, dist=None, refine_intrinsics=(), cam_group=None,
+                       loss: str = "linear", f_scale: float = 1.0) -> dict:
+    """Linearise the global problem with intrinsics (``sfmhip_ba_calib_linearize``), the arguments
+    of :func:`bundle_adjust`.  As :func:`ba_global_linearize`, plus Jk (M,2,5) = d r / d theta
+    (columns of components that are not refined are 0), B (C,6,5), H (G,5,5), g_k (G,5) and the
+    tensors ``theta`` (G,5), ``asp`` (G,), ``cam_group`` (C,), ``mask`` (5,) the matvec needs."""
+    require_gpu()
+    code, f_scale = _ba_loss(loss, f_scale)
+    d = _calib_inputs(_ba_global_inputs(cam, K, X, obs_cam, obs_pt, pts2d), dist, refine_intrinsics, cam_group)
+    C, N, M, G = d["C"], d["N"], d["M"], d["G"]
+    dv = d["cam"].device
+    for name, shape in (("r", (M, 2)), ("Jc", (M, 2, 6)), ("Jk", (M, 2, 5)), ("Jp", (M, 2, 3)), ("U", (C, 6, 6)),
+                        ("g_c", (C, 6)), ("B", (C, 6, 5)), ("H", (G, 5, 5)), ("g_k", (G, 5)), ("V", (N, 3, 3)),
+                        ("g_p", (N, 3)), ("weight", (M,))):
+        d[name] = torch.empty(shape, dtype=torch.float64, device=dv)
+    cost = ctypes.c_double(0.0)
+    call("sfmhip_ba_calib_linearize", ptr(d["cam"]), ptr(d["theta"]), ptr(d["asp"]), ptr(d["cam_group"]),
+         ptr(d["mask"]), ptr(d["X"]), ptr(d["obs_cam"]), ptr(d["obs_pt"]), ptr(d["pts2d"]), ptr(d["pt_off"]),
+         ptr(d["cam_perm"]), ptr(d["cam_off"]), C, N, G, M, ptr(d["r"]), ptr(d["Jc"]), ptr(d["Jk"]), ptr(d["Jp"]),
+         ptr(d["U"]), ptr(d["g_c"]), ptr(d["B"]), ptr(d["H"]), ptr(d["g_k"]), ptr(d["V"]), ptr(d["g_p"]),
+         ctypes.addressof(cost), stream_ptr(), code, f_scale, ptr(d["weight"]))
+    d["cost"] = cost.value
+    return d
+
+
+def ba_calib_matvec(lin: dict, x, lam: float, cam_fixed=None) -> torch.Tensor:
+    """out (6C + 5G,) = S~(lam) x~ of the linearisation ``lin`` (:func:`ba_calib_linearize`),
+    matrix-free; x~ = (x_c (C,6) flattened, x_k (G,5) flattened).  Rows of fixed cameras and of
+    components that are not refined are exactly 0.  ``lam`` as in :func:`ba_global_schur_matvec`."""
+    require_gpu()
+    C, N, M, G = lin["C"], lin["N"], lin["M"], lin["G"]
+    n = 6 * C + 5 * G
+    xt = dev(np.asarray(x, np.float64).reshape(n) if not isinstance(x, torch.Tensor) else x, torch.float64)
+    if tuple(xt.shape) != (n,):
+        raise ValueError("x must be (6 C + 5 G,)")
+    fx = None if cam_fixed is None else _fixed_tensor(cam_fixed, C)
+    out = torch.empty((n,), dtype=torch.float64, device=xt.device)
+    call("sfmhip_ba_calib_matvec", ptr(lin["Jc"]), ptr(lin["Jk"]), ptr(lin["Jp"]), ptr(lin["U"]), ptr(lin["B"]),
+         ptr(lin["H"]), ptr(lin["V"]), ptr(lin["cam_group"]), ptr(lin["mask"]), ptr(lin["obs_cam"]),
+         ptr(lin["obs_pt"]), ptr(lin["pt_off"]), ptr(lin["cam_perm"]), ptr(lin["cam_off"]), ptr(fx), C, N, G, M,
+         float(lam), ptr(xt), ptr(out), stream_ptr())
+    return out
+
+
+def undistort_points(src, K, dist) -> np.ndarray:
+    """Pixels (n,2) seen through the radial model (K, dist = k1, k2) -> the pixels (n,2) the same
+    K gives without distortion (``sfmhip_undistort_points``: 20 fixed-point steps per point), so
+    keypoints can go back through the pinhole stages."""
+    require_gpu()
+    K = np.asarray(K, np.float64).reshape(3, 3)
+    if K[0, 1] != 0:
+        raise ValueError("the camera matrix must have zero skew")
+    k1, k2 = _calib_dist(dist)[0]
+    s = dev(np.ascontiguousarray(np.asarray(src, np.float64).reshape(-1, 2)), torch.float64)
+    out = torch.empty_like(s)
+    call("sfmhip_undistort_points", ptr(s), int(s.shape[0]), float(K[0, 0]), float(K[1, 1]), float(K[0, 2]),
+         float(K[1, 2]), float(k1), float(k2), ptr(out), stream_ptr())
+    return out.cpu().numpy()
+
+
+def undistortPoints(src, cameraMatrix, distCoeffs):
+    """``cv2.undistortPoints(src, cameraMatrix, distCoeffs, P=cameraMatrix)`` for the radial
+    model (p1 = p2 = k3 = 0): (n,1,2) pixel coordinates under the same camera matrix."""
+    return undistort_points(src, cameraMatrix, distCoeffs).reshape(-1, 1, 2)
+
+
 def bundle_adjust(cam, K, X, obs_cam, obs_pt, pts2d, cam_fixed=None, gtol: float = 1e-8, ftol: float = 1e-10,
-                  eta: float = 1e-2, max_iter: int = 50, max_cg: int = 64, loss: str = "linear", f_scale: float = 1.0):
+                  eta: float = 1e-2, max_iter: int = 50, max_cg: int = 64, loss: str = "linear", f_scale: float = 1.0,
+                  dist=None, refine_intrinsics=(), cam_group=None):
     """Global bundle adjustment of all cameras and points (``sfmhip_ba_global_robust``).
 
     cam (C,6) = rvec, t (world -> camera); K (3,3) or (C,3,3), held fixed; X (N,3);
@@ -454,9 +594,21 @@ def bundle_adjust(cam, K, X, obs_cam, obs_pt, pts2d, cam_fixed=None, gtol: float
     ``least_squares`` does: z = |r|^2 / f_scale^2, cost = 0.5 f_scale^2 sum rho(z) with
     scipy's rho, weights w = rho'(z) (plain IRLS, no second-order correction).
     ``cost0`` and ``cost`` are that robust cost.  Cauchy with f_scale of 1-2 px
-    converges on gross outliers; Huber under IRLS creeps."""
+    converges on gross outliers; Huber under IRLS creeps.
+
+    Intrinsics (``sfmhip_ba_calib``, DESIGN.md "K3''' with intrinsics"): ``dist`` = (k1, k2), one
+    row per intrinsics group or one for all (a cv2 distortion vector is accepted when p1, p2 and
+    k3 are 0), puts OpenCV's radial model between the normalised point and the pixel;
+    ``refine_intrinsics``, a subset of {"f", "pp", "k1", "k2"}, frees the focal length (the
+    aspect fy / fx of the input K stays), the principal point and the two coefficients;
+    ``cam_group`` (C,) maps every camera to its intrinsics group (default: one shared camera; the
+    K of a group's cameras must be equal and have zero skew).  With ``dist`` None and nothing to
+    refine the call is the pinhole solve above, unchanged.  Otherwise the result also carries
+    ``K`` (C,3,3), ``dist`` (G,2) and ``theta`` (G,5) = f, cx, cy, k1, k2, and ``residual`` /
+    ``weight`` are those of the distorted model."""
     require_gpu()
     code, f_scale = _ba_loss(loss, f_scale)
+    calib = dist is not None or bool(_calib_mask(refine_intrinsics).any())
     d = _ba_global_inputs(cam, K, X, obs_cam, obs_pt, pts2d)
     C, N, M = d["C"], d["N"], d["M"]
     if cam_fixed is None:
@@ -467,6 +619,19 @@ def bundle_adjust(cam, K, X, obs_cam, obs_pt, pts2d, cam_fixed=None, gtol: float
     cost = (ctypes.c_double * 2)()
     info = (ctypes.c_int32 * 4)()
     res2 = torch.full((M,), float("nan"), dtype=torch.float64, device=camt.device)
+    if calib:
+        d = _calib_inputs(d, dist, refine_intrinsics, cam_group)
+        tht = d["theta"].clone()
+        call("sfmhip_ba_calib", ptr(camt), ptr(tht), ptr(d["asp"]), ptr(d["cam_group"]), ptr(d["mask"]), ptr(Xt),
+             ptr(d["obs_cam"]), ptr(d["obs_pt"]), ptr(d["pts2d"]), ptr(d["pt_off"]), ptr(d["cam_perm"]),
+             ptr(d["cam_off"]), ptr(fx), C, N, d["G"], M, float(gtol), float(ftol), float(eta), int(max_iter),
+             int(max_cg), ctypes.addressof(cost), ctypes.addressof(info), stream_ptr(), code, f_scale, ptr(res2))
+        theta = tht.cpu().numpy()
+        return _BundleResult(cam=camt.cpu().numpy(), X=Xt.cpu().numpy(), cost0=cost[0], cost=cost[1],
+                             status=int(info[0]), nit=int(info[1]), n_accept=int(info[2]), n_cg=int(info[3]),
+                             loss=loss, f_scale=f_scale, _res2=res2, _order=d["order"], theta=theta,
+                             dist=theta[:, 3:].copy(),
+                             K=_calib_K(theta, d["asp"].cpu().numpy(), d["cam_group"].cpu().numpy()))
     call("sfmhip_ba_global_robust", ptr(camt), ptr(d["K"]), ptr(Xt), ptr(d["obs_cam"]), ptr(d["obs_pt"]),
          ptr(d["pts2d"]), ptr(d["pt_off"]), ptr(d["cam_perm"]), ptr(d["cam_off"]), ptr(fx), C, N, M, float(gtol),
          float(ftol), float(eta), int(max_iter), int(max_cg), ctypes.addressof(cost), ctypes.addressof(info),

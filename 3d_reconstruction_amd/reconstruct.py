@@ -102,7 +102,7 @@ def incremental_sfm(img_pairs, all_matches, all_points, all_colors, n_images: in
 
 def global_refine(cameras, all_point3ds, img_pairs, all_matches, all_points, focal: float = FOCAL,
                   gate_px: float = 4.0, fixed=None, loss: str = "linear", f_scale: float = 1.0, reject_px=None,
-                  polish: bool = False, **solver):
+                  polish: bool = False, refine_intrinsics=(), **solver):
     """Global bundle adjustment of an :func:`incremental_sfm` result, in place
     (geometry.bundle_adjust; not part of the reference, whose loop only adjusts
     camera j and the new points of each pair).
@@ -134,9 +134,15 @@ def global_refine(cameras, all_point3ds, img_pairs, all_matches, all_points, foc
     ``all_point3ds[0]`` and ``all_point3ds[1]``.  The result (of the polish when there is
     one) gains ``inlier`` (bool, over the gated list) and ``robust`` (the first solve's
     result when polished, else ``None``; the polish's own ``residual`` covers only the
-    observations it used)."""
+    observations it used).
+
+    ``refine_intrinsics`` (a subset of {"f", "pp", "k1", "k2"}, see bundle_adjust) also refines the
+    one camera all images share: the focal length starts at ``focal``, the distortion at 0 (so the
+    pinhole gate above is right as it stands), and the result carries the refined ``K`` and
+    ``dist``; a polish starts from them.  Empty (the default): the pinhole calls, unchanged."""
     from .geometry import _residual, bundle_adjust
     robust = loss != "linear"
+    calib = dict(refine_intrinsics=refine_intrinsics) if len(refine_intrinsics) else {}
     if not robust and (polish or reject_px is not None):
         raise ValueError("reject_px and polish need a robust loss")
     K = np.array([[focal, 0, 0], [0, focal, 0], [0, 0, 1.0]])
@@ -177,7 +183,8 @@ def global_refine(cameras, all_point3ds, img_pairs, all_matches, all_points, foc
         fixed = () if first is None else (first,)
     cam_fixed = np.isin(cams, np.asarray(list(fixed), np.int64)).astype(np.uint8)
     if robust:
-        first = bundle_adjust(cam6, K, X, cam_idx, tr_idx, uv, cam_fixed=cam_fixed, loss=loss, f_scale=f_scale, **solver)
+        first = bundle_adjust(cam6, K, X, cam_idx, tr_idx, uv, cam_fixed=cam_fixed, loss=loss, f_scale=f_scale, **calib,
+                              **solver)
         res, inlier = first, np.zeros(len(oc), bool)
         if first.status >= 0:
             limit = reject_px if reject_px is not None else (gate_px if np.isfinite(gate_px) else 4.0)
@@ -185,8 +192,9 @@ def global_refine(cameras, all_point3ds, img_pairs, all_matches, all_points, foc
             alive = np.bincount(tr_idx[inlier], minlength=len(trs)) >= 2
             if polish:
                 use = inlier & alive[tr_idx]
-                res = bundle_adjust(first.cam, K, first.X, cam_idx[use], tr_idx[use], uv[use], cam_fixed=cam_fixed,
-                                    **solver)
+                again = dict(calib, dist=first.dist) if calib else {}
+                res = bundle_adjust(first.cam, first.K[0] if calib and len(cams) else K, first.X, cam_idx[use],
+                                    tr_idx[use], uv[use], cam_fixed=cam_fixed, **again, **solver)
             for k, c in enumerate(cams):
                 if not cam_fixed[k]:
                     cameras[c] = np.hstack((Rodrigues(res.cam[k, :3])[0], res.cam[k, 3:].reshape(3, 1)))
@@ -198,7 +206,7 @@ def global_refine(cameras, all_point3ds, img_pairs, all_matches, all_points, foc
         res.n_candidates = len(cand)
         res.obs_cam, res.obs_track, res.pts2d = oc, ot, uv
         return res, len(oc)
-    res = bundle_adjust(cam6, K, X, cam_idx, tr_idx, uv, cam_fixed=cam_fixed, **solver)
+    res = bundle_adjust(cam6, K, X, cam_idx, tr_idx, uv, cam_fixed=cam_fixed, **calib, **solver)
     if res.status >= 0:
         for k, c in enumerate(cams):
             if not cam_fixed[k]:

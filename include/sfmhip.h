@@ -377,6 +377,56 @@ int sfmhip_ba_global_robust(double* cam, const double* K, double* X, const int32
                             double ftol, double eta, int max_iter, int max_cg, double* cost, int32_t* info,
                             void* stream, int loss, double f_scale, double* obs_res2);
 
+/* ---- K3''' with intrinsics: shared intrinsics and radial distortion as unknowns (ba_calib.hip;
+ * DESIGN.md "K3''' with intrinsics", tests/ba_calib_ref.py restates every step).
+ * Every camera belongs to one of G intrinsics groups: cam_group [C] int32 in [0, G).  A group holds
+ * theta [G][5] = (f, cx, cy, k1, k2) and a fixed aspect asp [G] = fy / fx (zero skew):
+ *   (x, y, z) = R X + t, xn = x / z, yn = y / z, r2 = xn^2 + yn^2, d = 1 + k1 r2 + k2 r2^2,
+ *   u = f (d xn) + cx, v = (f asp) (d yn) + cy        (OpenCV's radial model with p1 = p2 = k3 = 0).
+ * mask [5] uint8 (device, each 0 or 1; the same for every group): 1 = the component of theta is
+ * free.  Everything else — the sorted observation layout, cam_fixed, the left perturbation of a
+ * camera, the loss codes and f_scale, the step rule, tolerances, cost[2], info[4], the status codes
+ * and obs_res2 — is as in sfmhip_ba_global_robust.  The camera-side unknown is x~ = (x_c [6C],
+ * x_k [5G]), the intrinsics after the cameras.  No floating-point atomics; a group's sums add the
+ * per-camera values in ascending camera index (lane l of 256 takes the group's l-th, (l+256)-th, ...
+ * camera in sequence, then the pairwise tree), so two runs give the same bits.
+ *
+ * sfmhip_ba_calib_linearize: r [M][2], Jc [M][2][6], Jk [M][2][5] = d r / d theta (columns of masked
+ * components 0), Jp [M][2][3] in sorted order, weighted by sqrt(w) under a robust loss; U [C][6][6],
+ * g_c [C][6], B [C][6][5] = sum Jc^T Jk, H [G][5][5] = sum Jk^T Jk, g_k [G][5] = sum Jk^T r,
+ * V [N][3][3], g_p [N][3], *cost, weight [M] (nullable).  Blocking.
+ * sfmhip_ba_calib_matvec: out [6C + 5G] = S~(lambda) x~ with
+ *   S~ x~ = [U* x_c + B x_k ; sum_c B^T x_c + H* x_k] - A~^T Jp V*^-1 Jp^T A~ x~,  A~ = [Jc | Jk];
+ * observations of a fixed camera still act through Jk.  Entries of x at fixed cameras and masked
+ * components are not read; their rows of out are exactly 0.
+ * sfmhip_ba_calib: the whole solve; cam, theta and X are updated in place.  A fixed camera, a camera
+ * or point without observations, a masked component and a group without cameras come back
+ * bit-unchanged.  With k1 = k2 = 0, an empty mask and fy == f asp in floating point (square pixels
+ * for one) every value equals sfmhip_ba_global_robust's.
+ * Sizes: as sfmhip_ba_global, and G <= 2^20; C > 0 needs G > 0.  */
+int sfmhip_ba_calib_linearize(const double* cam, const double* theta, const double* asp, const int32_t* cam_group,
+                              const uint8_t* mask, const double* X, const int32_t* obs_cam, const int32_t* obs_pt,
+                              const double* pts2d, const int64_t* pt_off, const int64_t* cam_perm,
+                              const int64_t* cam_off, int C, int N, int G, int64_t M, double* r, double* Jc,
+                              double* Jk, double* Jp, double* U, double* g_c, double* B, double* H, double* g_k,
+                              double* V, double* g_p, double* cost, void* stream, int loss, double f_scale,
+                              double* weight);
+int sfmhip_ba_calib_matvec(const double* Jc, const double* Jk, const double* Jp, const double* U, const double* B,
+                           const double* H, const double* V, const int32_t* cam_group, const uint8_t* mask,
+                           const int32_t* obs_cam, const int32_t* obs_pt, const int64_t* pt_off,
+                           const int64_t* cam_perm, const int64_t* cam_off, const uint8_t* cam_fixed, int C, int N,
+                           int G, int64_t M, double lambda, const double* x, double* out, void* stream);
+int sfmhip_ba_calib(double* cam, double* theta, const double* asp, const int32_t* cam_group, const uint8_t* mask,
+                    double* X, const int32_t* obs_cam, const int32_t* obs_pt, const double* pts2d,
+                    const int64_t* pt_off, const int64_t* cam_perm, const int64_t* cam_off, const uint8_t* cam_fixed,
+                    int C, int N, int G, int64_t M, double gtol, double ftol, double eta, int max_iter, int max_cg,
+                    double* cost, int32_t* info, void* stream, int loss, double f_scale, double* obs_res2);
+/* Inverse of the radial model above for pixels: src, dst [n][2] (device).  20 fixed-point steps
+ * xn <- xd / d(xn) from the distorted normalised point; dst is the pixel under the same fx, fy, cx,
+ * cy with zero distortion.  */
+int sfmhip_undistort_points(const double* src, int64_t n, double fx, double fy, double cx, double cy, double k1,
+                            double k2, double* dst, void* stream);
+
 /* ---- V1: voxel_traversal (voxel_travesal.py:1-73), quirks included -------
  * rays [N][8] f32 = o(3), d(3), near, far.  Pass 1 counts per-ray steps
  * (n_steps[N]; a ray still active after max_steps reports max_steps + 1),

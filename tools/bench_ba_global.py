@@ -12,8 +12,13 @@ iterations, bit for bit).
     python tools/bench_ba_global.py [--scipy-nfev 10] [--cams 257 --points 100000 --vis 0.03]
     python tools/bench_ba_global.py --loss cauchy --f-scale 1 --outliers 0.05 --ftol 1e-8
 
+    python tools/bench_ba_global.py --refine f,k1,k2 --k1 -0.12 --k2 0.03 --ftol 1e-8
+
 --loss / --f-scale choose the robust loss of bundle_adjust (default: linear); --outliers displaces
 that fraction of the observations by 20-100 px (the generator of tests/test_gpu_ba_robust.py).
+--refine (a comma list of f, pp, k1, k2) times the solve with intrinsics (ba_calib.hip) from zero
+distortion; --k1 / --k2 move the rendered observations to where a camera with that radial
+distortion sees them.  Without --refine the pinhole arm runs exactly as before.
 """
 import argparse
 import importlib
@@ -40,6 +45,9 @@ ap.add_argument("--ftol", type=float, default=1e-10)
 ap.add_argument("--loss", default="linear", choices=["linear", "huber", "soft_l1", "cauchy"])
 ap.add_argument("--f-scale", type=float, default=1.0)
 ap.add_argument("--outliers", type=float, default=0.0, help="fraction of observations displaced by 20-100 px")
+ap.add_argument("--refine", default="", help="comma list of f, pp, k1, k2: refine these intrinsics (ba_calib.hip)")
+ap.add_argument("--k1", type=float, default=0.0, help="radial distortion of the rendered observations")
+ap.add_argument("--k2", type=float, default=0.0)
 ap.add_argument("--scipy-nfev", type=int, default=0, help="0 skips the scipy arm")
 a = ap.parse_args()
 
@@ -50,8 +58,17 @@ if a.outliers > 0:
     bad = rng.random(len(s["obs_cam"])) < a.outliers
     n_out = int(bad.sum())
     s["pts2d"][bad] += rng.uniform(20.0, 100.0, (n_out, 2)) * rng.choice([-1.0, 1.0], (n_out, 2))
+if a.k1 != 0.0 or a.k2 != 0.0:
+    xn = s["pts2d"] / syn.FOCAL
+    r2 = (xn * xn).sum(1, keepdims=True)
+    s["pts2d"] = (1.0 + a.k1 * r2 + a.k2 * r2 * r2) * xn * syn.FOCAL
+refine = tuple(k for k in a.refine.split(",") if k)
+if refine:
+    assert a.scipy_nfev == 0, "the scipy arm is the pinhole model"
 # the linear loss goes through the default arguments, as every caller before the robust loss did
 loss_kw = {} if a.loss == "linear" else dict(loss=a.loss, f_scale=a.f_scale)
+if refine:
+    loss_kw["refine_intrinsics"] = refine
 args = (s["cam"], s["K"], s["X"], s["obs_cam"], s["obs_pt"], s["pts2d"], s["cam_fixed"])
 M = len(s["obs_cam"])
 
@@ -73,22 +90,26 @@ for _ in range(3):
     sfm.ba_global_structure(s["obs_cam"], s["obs_pt"], a.cams, a.points)
 host_ms = (time.perf_counter() - t0) / 3 * 1e3
 # launches: a trial step = damp + 2 (right-hand side) + CG init + 3 per CG slot + back-substitution
-# + trial + 2 (trial cost) + step + accept; a linearisation = 5 + the gate
+# + trial + 2 (trial cost) + step + accept; a linearisation = 5 + the gate.  With intrinsics the group
+# pass adds one launch to the right-hand side and to every CG slot, and a linearisation has 8 + the gate
+per_slot = 4 if refine else 3
 out = dict(C=a.cams, N=a.points, M=M, loss=a.loss, f_scale=a.f_scale, outliers=n_out, ms_per_solve=round(ms, 2), host_structure_ms=round(host_ms, 2), status=res.status,
            linearisations=res.nit, accepted=res.n_accept, cg_iterations=res.n_cg, cost0=res.cost0, cost=res.cost,
-           launches_per_trial=10 + 3 * 64, launches_per_linearisation=6)
+           launches_per_trial=(11 if refine else 10) + per_slot * 64, launches_per_linearisation=9 if refine else 6)
+if refine:
+    out.update(refine=list(refine), k1=a.k1, k2=a.k2, theta=res.theta.tolist())
 for k in (8, 12, 16, 24, 32, 48):
     ms_k, res_k = timed(k, a.reps)
     if (res_k.n_cg, res_k.nit, res_k.cost) == (res.n_cg, res.nit, res.cost):
-        # same iterations with 3 * (64 - k) fewer launches per trial, all of them no-ops; the slots
+        # same iterations with per_slot * (64 - k) fewer launches per trial, all of them no-ops; the slots
         # of the shorter batch that still go unused cost the same each
         # the result reports accepted steps, not trial steps: a rejected trial runs one more CG batch
         # that cannot be counted from here, and would understate the no-op launches and their cost;
         # the output names the assumption (it holds when the cost falls at every trial, as on this scene)
         trials = max(res.n_accept, 1)
         out["trials_assumed"] = "every trial accepted (rejected trials are not reported by the solver)"
-        per_noop_ms = (ms - ms_k) / (3 * (64 - k) * trials)
-        noops = 3 * (64 * trials - res.n_cg)
+        per_noop_ms = (ms - ms_k) / (per_slot * (64 - k) * trials)
+        noops = per_slot * (64 * trials - res.n_cg)
         out.update(max_cg_same_result=k, ms_at_that_max_cg=round(ms_k, 2), us_per_noop_launch=round(per_noop_ms * 1e3, 2),
                    noop_launches=noops, noop_share=round(per_noop_ms * noops / ms, 3))
         break
