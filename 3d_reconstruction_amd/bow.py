@@ -40,7 +40,9 @@ def kmeans(obs, k_or_guess, iter: int = 20, thresh: float = 1e-5, check_finite: 
     if check_finite and not np.isfinite(o_np).all():
         raise ValueError("array must not contain infs or NaNs")
     if o_np.ndim == 1:
-        o_np = o_np[:, None]
+        # 1-D observations: scipy's code book is 1-D too
+        book, dist = kmeans(o_np[:, None], k_or_guess, iter, thresh, False, rng=rng)
+        return book[:, 0], dist
     o = dev(o_np, torch.float64)
     guess = np.asarray(k_or_guess)
     if iter < 1:

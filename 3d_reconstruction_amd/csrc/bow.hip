@@ -93,8 +93,9 @@ extern "C" int sfmhip_word_histogram(const int32_t* codes, const int64_t* offset
 
 extern "C" int sfmhip_kmeans_update(const double* obs, int64_t n, int d, const int32_t* codes, int k,
                                     double* book, int32_t* counts, void* stream) {
-    SFMHIP_REQUIRE(obs && codes && book && counts, "sfmhip_kmeans_update: null pointer");
     SFMHIP_REQUIRE(n >= 0 && d > 0 && d <= 1024 && k > 0, "sfmhip_kmeans_update: bad shape (d <= 1024)");
+    // n = 0 reads neither obs nor codes (an empty tensor's pointer is null): every count is 0, book stays
+    SFMHIP_REQUIRE(book && counts && (n == 0 || (obs && codes)), "sfmhip_kmeans_update: null pointer");
     hipLaunchKernelGGL(kmeans_update_kernel, dim3(k), dim3(256), 0, as_stream(stream), obs, n, d, codes, k, book,
                        counts);
     return check_launch("kmeans_update_kernel");

@@ -26,7 +26,7 @@ __global__ __launch_bounds__(256) void vq_kernel(const double* __restrict__ obs,
                                                  int32_t* __restrict__ codes, double* __restrict__ dist) {
     extern __shared__ double smem[];
     double* sobs = smem;                                   // [16][d]
-    double* scode = smem + kVqObsPerBlock * d;             // [64][d + 1]
+    double* scode = smem + kVqObsPerBlock * d;             // [32][d + 1]
     const int ld = d + 1;
     const int64_t o0 = (int64_t)blockIdx.x * kVqObsPerBlock;
     for (int t = threadIdx.x; t < kVqObsPerBlock * d; t += blockDim.x) {
@@ -553,6 +553,9 @@ extern "C" int sfmhip_vq(const double* obs, int64_t n_obs, const double* code_bo
     SFMHIP_REQUIRE(blocks < INT_MAX, "sfmhip_vq: too many observations");
     const size_t shm = (size_t)(kVqObsPerBlock * d + kVqCodesPerChunk * (d + 1)) * sizeof(double);
     SFMHIP_REQUIRE(shm <= 160 * 1024, "sfmhip_vq: descriptor dim too large for the LDS tiles");
+    // more than 64 KB of dynamic LDS from d = 171 on (98,560 B at d = 256): declared as for the two
+    // kernels above (the launch was accepted without it when measured; kept so all three agree)
+    (void)hipFuncSetAttribute((const void*)vq_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
     hipLaunchKernelGGL(vq_kernel, dim3((int)blocks), dim3(256), shm, as_stream(stream), obs, n_obs, code_book,
                        n_codes, d, codes, dist);
     return check_launch("vq_kernel");

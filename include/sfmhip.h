@@ -228,7 +228,8 @@ int sfmhip_word_histogram(const int32_t* codes, const int64_t* offsets, int n_im
 
 /* scipy.cluster.vq.kmeans centroid update (bow.py:23 -> _vq.update_cluster_means):
  * per cluster, the f64 sum of its observations in index order, / count.
- * book [k][d] rows of empty clusters are left untouched; counts [k].          */
+ * book [k][d] rows of empty clusters are left untouched; counts [k].
+ * n = 0 zeroes counts and leaves book as it is; obs and codes may then be null. */
 int sfmhip_kmeans_update(const double* obs, int64_t n, int d, const int32_t* codes, int k,
                          double* book, int32_t* counts, void* stream);
 
