@@ -24,9 +24,10 @@ from .voxel import (MASK_PLENOXEL, MASK_SDF, VoxelGrid, icp_normal_equations, ic
                     tsdf_layer_stats, tsdf_raycast, tsdf_track, voxel_traversal)
 from .mvs import census_transform, depth_consistency, inverse_depth_planes, mvs_depth, plane_sweep  # noqa: F401
 from .mvs import cost_volume, sgm_aggregate, volume_select  # noqa: F401
+from .rectify import optimal_new_K, undistort_depth, undistort_images, undistort_map  # noqa: F401
 from .features import (sift, sift_describe, sift_detect, sift_orient, sift_pyramid,  # noqa: F401
                        sift_tables)
-from . import bow, features, mesh, mvs, pipeline, reconstruct, tracks, verify  # noqa: F401,E402
+from . import bow, features, mesh, mvs, pipeline, reconstruct, rectify, tracks, verify  # noqa: F401,E402
 from .mesh import write_ply  # noqa: F401
 from .bow import kmeans  # noqa: F401
 from .reconstruct import triangulate  # noqa: F401

@@ -135,6 +135,9 @@ SIGNATURES = {
     "sfmhip_sgm_aggregate": [_p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p],
     "sfmhip_volume_select": [_p, _p, _p, _i32, _i32, _i32, _p, _p, _i32, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p,
                              _p],
+    "sfmhip_undistort_u8": [_p, _i32, _i32, _i32, _i32, _p, _p, _i32, _i32, _p, _p, _p],
+    "sfmhip_undistort_f32": [_p, _i32, _i32, _i32, _p, _p, _i32, _i32, _p, _p],
+    "sfmhip_undistort_map": [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p],
     "sfmhip_sift_pyramid": [_p, _i32, _i32, _i32, _i32, _p, _p, _p, _p],
     "sfmhip_sift_detect": [_p, _i32, _i32, _i32, _i32, _p, _i32, _f32, _f32, _f32, _i32, _p, _p, _p],
     "sfmhip_sift_orient": [_p, _i32, _i32, _i32, _i32, _p, _p, _i32, _p, _i32, _p, _p, _p],

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from ._abi import call, dev, ptr, require_gpu, stream_ptr
+from .rectify import undistort_images
 
 
 def inverse_depth_planes(near: float, far: float, P: int) -> np.ndarray:
@@ -343,7 +344,8 @@ def depth_consistency(depth, poses, K, refs, srcs, eps: float = 0.01, min_consis
 
 
 def mvs_depth(images, poses, K, neighbours, planes, agg_radius: int = 2, penalty: int = 24, uniq: int = 243,
-              min_views: int = 2, eps: float = 0.01, min_consistent: int = 2, smooth=None) -> torch.Tensor:
+              min_views: int = 2, eps: float = 0.01, min_consistent: int = 2, smooth=None, *,
+              dist=None) -> torch.Tensor:
     """Depth maps of V posed images: one census, a plane sweep of every view against its own
     sources, and the cross-view consistency filter.
 
@@ -354,10 +356,15 @@ def mvs_depth(images, poses, K, neighbours, planes, agg_radius: int = 2, penalty
     padded; a view with an empty list stays all-invalid.  ``smooth=(p1, p2[, paths])`` sweeps
     with semi-global smoothing as :func:`plane_sweep` does, one view at a time through one
     cost volume and one aggregated volume, so the memory is that of one view.
+    ``dist`` (as for :func:`~.rectify.undistort_images`): the images were taken through the
+    radial model (K, dist); they are first resampled to the pinhole camera of the same K and
+    size, and the depth maps are that camera's.
 
     Returns depth (V,H,W) f32 on the device with 0 = invalid:
     :func:`~.voxel.tsdf_integrate` takes it as it is, with the same poses and K."""
     gpu = require_gpu()
+    if dist is not None:
+        images = undistort_images(images, K, dist)[0]
     cen = census_transform(images)
     V, H, W = cen.shape
     ps, kk = _cameras(poses, K, V)

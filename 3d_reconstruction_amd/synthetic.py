@@ -310,13 +310,16 @@ def _value_noise(X, cell):
     return out
 
 
-def mvs_scene(Hd=192, Wd=256, focal=220.0, cx=128.0, cy=96.0, n_views=5, device="cpu"):
+def mvs_scene(Hd=192, Wd=256, focal=220.0, cx=128.0, cy=96.0, n_views=5, device="cpu", dist=None):
     """Posed grey images of :func:`tsdf_scene`'s floor and spheres for multi-view stereo: camera
     i at (3 cos a, 2.2, 3 sin a), a = 90 + 5 (i - 2) degrees, looking at the origin.  The depth
     is analytic in f64 (the ray maths of :func:`tsdf_scene`) and rounded to f32; the grey value
     of a pixel is clip(rint(0.6 N(X, 0.08) + 0.4 N(X + 17.3, 0.036)), 0, 255) at its world hit
     point X (f64 back-projection as in :func:`tsdf_scene_colour`), N trilinear value noise, so
     the views agree on the texture of a surface point; 0 where a ray hits nothing.
+    ``dist=(k1, k2)`` renders through the radial model: a pixel's ray is that of its undistorted
+    normalised point (the 20 fixed-point steps of ``undistort_points``), and the depth is the z
+    along that ray.
     Returns grey (V,Hd,Wd) u8, depth (V,Hd,Wd) f32, poses (V,3,4) f32, K (V,4) f32."""
     f64 = torch.float64
     us = torch.arange(Wd, device=device, dtype=f64)[None, :]
@@ -325,6 +328,15 @@ def mvs_scene(Hd=192, Wd=256, focal=220.0, cx=128.0, cy=96.0, n_views=5, device=
     K = np.tile(np.array([[focal, focal, cx, cy]], np.float32), (n_views, 1))
     depth = torch.empty((n_views, Hd, Wd), dtype=torch.float32, device=device)
     grey = torch.zeros((n_views, Hd, Wd), dtype=torch.uint8, device=device)
+    xn, yn = (us - cx) / focal, (vs - cy) / focal
+    if dist is not None:
+        k1, k2 = (float(k) for k in dist)
+        xd, yd = torch.broadcast_tensors(xn, yn)
+        xn, yn = xd, yd
+        for _ in range(20):
+            r2 = xn * xn + yn * yn
+            d = (1.0 + k1 * r2) + k2 * (r2 * r2)
+            xn, yn = xd / d, yd / d
     for i in range(n_views):
         a = math.radians(90.0 + 5.0 * (i - 2))
         c_np = np.array([3.0 * math.cos(a), 2.2, 3.0 * math.sin(a)])
@@ -332,8 +344,7 @@ def mvs_scene(Hd=192, Wd=256, focal=220.0, cx=128.0, cy=96.0, n_views=5, device=
         poses[i, :, :3], poses[i, :, 3] = R_np, t_np
         R = torch.tensor(R_np, dtype=f64, device=device)
         c = torch.tensor(c_np, dtype=f64, device=device)
-        dc = torch.stack(torch.broadcast_tensors((us - cx) / focal, (vs - cy) / focal,
-                                                 torch.ones(1, device=device, dtype=f64)), -1)
+        dc = torch.stack(torch.broadcast_tensors(xn, yn, torch.ones(1, device=device, dtype=f64)), -1)
         dw = dc @ R
         best = torch.full(dw.shape[:2], float("inf"), device=device, dtype=f64)
         for (sx, sy, sz, sr) in SPHERES:
@@ -353,7 +364,10 @@ def mvs_scene(Hd=192, Wd=256, focal=220.0, cx=128.0, cy=96.0, n_views=5, device=
         d = depth[i].to(f64)
         P = torch.tensor(poses[i], dtype=f64, device=device)
         fx, fy, cxx, cyy = (float(x) for x in K[i])
-        pc = torch.stack(torch.broadcast_tensors((us - cxx) / fx * d, (vs - cyy) / fy * d, d), -1)
+        if dist is None:
+            pc = torch.stack(torch.broadcast_tensors((us - cxx) / fx * d, (vs - cyy) / fy * d, d), -1)
+        else:
+            pc = torch.stack(torch.broadcast_tensors(xn * d, yn * d, d), -1)
         X = (pc - P[:, 3]) @ P[:, :3]
         g = torch.clamp(torch.round(0.6 * _value_noise(X, 0.08) + 0.4 * _value_noise(X + 17.3, 0.036)), 0, 255)
         grey[i] = torch.where(d > 0, g, torch.zeros_like(g)).to(torch.uint8)

@@ -955,6 +955,59 @@ int sfmhip_depth_consistency(const float* depth, const float* poses, const float
                              const int32_t* refs, const int32_t* srcs, int R, int S, float eps,
                              int min_consistent, uint8_t* count, float* filtered, void* stream);
 
+/* ---- V12: undistortion of images and depth maps for the dense path (build-defined)
+ * V10 and V5 - V9 take pinhole cameras.  These calls resample V views seen through the
+ * radial model of the calibrating bundle adjustment (sfmhip_ba_calib) to pinhole
+ * views, a gather per output pixel.  The reference has no counterpart.  Restated in
+ * numpy by tests/undistort_ref.py.  The map is f64, one IEEE round-to-nearest step per
+ * operation in the order written, no FMA; the blend is integer: every output is
+ * defined to the bit.
+ *
+ * Cameras (device memory): cam_src [V][6] f64 = fx, fy, cx, cy, k1, k2 (OpenCV's radial
+ * model with p1 = p2 = k3 = 0) of the source images [V][H][W]; cam_dst [V][4] f64 =
+ * gx, gy, ox, oy, the pinhole camera of the outputs [V][Ho][Wo].  Pixel centres at
+ * integer coordinates.  View skip rule: a non-finite number among the 10 of a view,
+ * one of magnitude >= 2^60, or fx, fy, gx or gy of 0 makes every output pixel of the
+ * view invalid.
+ *
+ * The map of output pixel (u, v):
+ *   x = (u - ox) / gx;  y = (v - oy) / gy;  r2 = x x + y y;  r4 = r2 r2;
+ *   d = (1 + k1 r2) + k2 r4;  mono = (1 + (3 k1) r2) + (5 k2) r4   (the derivative of
+ *   r d(r): positive where the model has not folded over);
+ *   sx = (d x) fx + cx;  sy = (d y) fy + cy;
+ *   fin = mono > 0 and |sx| < 2^30 and |sy| < 2^30 (a NaN fails);
+ *   X = floor(sx 256 + 0.5), Y = floor(sy 256 + 0.5): integers, units of 1/256 px;
+ *   valid = fin and 0 <= X <= (W - 1) 256 and 0 <= Y <= (H - 1) 256.
+ * Validity is decided on the rounded X, Y: a source coordinate that misses the border
+ * by less than 1/512 px is inside.
+ *
+ * sfmhip_undistort_map: map [V][Ho][Wo][2] i32 = X, Y, or -1, -1 where invalid (8-byte
+ *   aligned).  Takes no image: H, W only bound X, Y.
+ * sfmhip_undistort_u8 (bilinear; C = 1, 3 or 4 interleaved channels, all alike):
+ *   x0 = X >> 8, a = X & 255, x1 = min(x0 + 1, W - 1); y0, b, y1 likewise from Y;
+ *   out = ((256-a)(256-b) p[y0][x0] + a (256-b) p[y0][x1] + (256-a) b p[y1][x0]
+ *          + a b p[y1][x1] + 32768) >> 16   (exact in u32);
+ *   mask [V][Ho][Wo] u8 = 1.  An invalid pixel: 0 in every channel and in the mask.
+ * sfmhip_undistort_f32 (nearest; for depth maps, whose z is unchanged by a radial
+ *   model and where 0 = invalid): the 32 bits of
+ *   src[min((Y + 128) >> 8, H - 1)][min((X + 128) >> 8, W - 1)], copied as they are (no
+ *   blending: no depth is invented across an edge); an invalid pixel: 0.
+ *
+ * Limits: V <= 65535; H, W, Ho, Wo <= 32768; C of 1, 3 or 4; dst 4-byte aligned when
+ * C = 4 and map 8-byte aligned: otherwise SFMHIP_E_ARG, like a null pointer, without
+ * touching the GPU.  V = 0, Ho Wo = 0, or for the two
+ * resampling calls H W = 0, is a no-op without a launch.  dst must not overlap src.
+ * Asynchronous plain launches on the stream (the x of every column and the y of every
+ * row of a view first, in scratch from the library pool; then one lane per output
+ * pixel); no atomics: two runs give the same bits.                                  */
+int sfmhip_undistort_u8(const uint8_t* src, int V, int H, int W, int C, const double* cam_src,
+                        const double* cam_dst, int Ho, int Wo, uint8_t* dst /* [V][Ho][Wo][C] */,
+                        uint8_t* mask /* [V][Ho][Wo] */, void* stream);
+int sfmhip_undistort_f32(const float* src, int V, int H, int W, const double* cam_src, const double* cam_dst,
+                         int Ho, int Wo, float* dst /* [V][Ho][Wo] */, void* stream);
+int sfmhip_undistort_map(const double* cam_src, const double* cam_dst, int V, int H, int W, int Ho, int Wo,
+                         int32_t* map /* [V][Ho][Wo][2] */, void* stream);
+
 /* ---- V11: SIFT keypoints and descriptors (build-defined) ---------------------
  * Scale-space extrema, orientation and the 128-d descriptor of V grey images, in
  * four calls.  The reference has no counterpart (it reads features from disk).
