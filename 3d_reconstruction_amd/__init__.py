@@ -25,9 +25,11 @@ from .voxel import (MASK_PLENOXEL, MASK_SDF, VoxelGrid, icp_normal_equations, ic
 from .mvs import census_transform, depth_consistency, inverse_depth_planes, mvs_depth, plane_sweep  # noqa: F401
 from .mvs import cost_volume, sgm_aggregate, volume_select  # noqa: F401
 from .rectify import optimal_new_K, undistort_depth, undistort_images, undistort_map  # noqa: F401
+from .plan import (DensePlan, cubic_grid, dense_inputs_from_reconstruction, obs_depth, plan_dense, plan_from_reconstruction, scene_bounds,  # noqa: F401
+                   segmented_select, select_sources, view_depth_ranges, view_pair_counts)
 from .features import (sift, sift_describe, sift_detect, sift_orient, sift_pyramid,  # noqa: F401
                        sift_tables)
-from . import bow, features, mesh, mvs, pipeline, reconstruct, rectify, tracks, verify  # noqa: F401,E402
+from . import bow, features, mesh, mvs, pipeline, plan, reconstruct, rectify, tracks, verify  # noqa: F401,E402
 from .mesh import write_ply  # noqa: F401
 from .bow import kmeans  # noqa: F401
 from .reconstruct import triangulate  # noqa: F401

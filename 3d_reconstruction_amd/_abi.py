@@ -138,7 +138,10 @@ SIGNATURES = {
     "sfmhip_undistort_u8": [_p, _i32, _i32, _i32, _i32, _p, _p, _i32, _i32, _p, _p, _p],
     "sfmhip_undistort_f32": [_p, _i32, _i32, _i32, _p, _p, _i32, _i32, _p, _p],
     "sfmhip_undistort_map": [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p],
-    "sfmhip_sift_pyramid": [_p, _i32, _i32, _i32, _i32, _p, _p, _p, _p],
+    "sfmhip_obs_depth": [_p, _i32, _p, _i64, _p, _p, _i64, _p, _p],
+    "sfmhip_view_pair_counts": [_p, _i32, _p, _i64, _p, _i64, _p, _f64, _f64, _p, _p, _p],
+    "sfmhip_segmented_select": [_p, _i64, _p, _i64, _p, _i32, _p, _p],
+    "sfmhip_sift_pyramid":[_p, _i32, _i32, _i32, _i32, _p, _p, _p, _p],
     "sfmhip_sift_detect": [_p, _i32, _i32, _i32, _i32, _p, _i32, _f32, _f32, _f32, _i32, _p, _p, _p],
     "sfmhip_sift_orient": [_p, _i32, _i32, _i32, _i32, _p, _p, _i32, _p, _i32, _p, _p, _p],
     "sfmhip_sift_describe": [_p, _i32, _i32, _i32, _i32, _p, _p, _i32, _p, _p, _p, _p, _p],

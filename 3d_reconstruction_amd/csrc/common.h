@@ -75,6 +75,7 @@ struct Knobs {
     int render_sort;    // SFMHIP_RENDER_SORT: 0 renders rays in input order (no spatial sort)
     int dda_direct;     // SFMHIP_DDA_DIRECT: fill kernel of the two-pass DDA (-1 auto, 0 staged, 1 direct)
     int raycast_skip;   // SFMHIP_RAYCAST_SKIP: 0 evaluates every sample of every ray (no box clipping, no brick skipping)
+    int plan_global;    // SFMHIP_PLAN_GLOBAL: 1 adds the view-pair counts straight to global memory (no LDS triangles)
     int ab;             // SFMHIP_AB: A/B selector for a form under measurement (0 = the default form)
 };
 Knobs knobs();

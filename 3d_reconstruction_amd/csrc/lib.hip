@@ -165,6 +165,7 @@ static Knobs read_knobs() {
     k.render_sort = env_knob("SFMHIP_RENDER_SORT", 1);
     k.dda_direct = env_knob("SFMHIP_DDA_DIRECT", -1);
     k.raycast_skip = env_knob("SFMHIP_RAYCAST_SKIP", 1);
+    k.plan_global = env_knob("SFMHIP_PLAN_GLOBAL", 0);
     k.ab = env_knob("SFMHIP_AB", 0);
     return k;
 }

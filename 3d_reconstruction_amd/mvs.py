@@ -351,9 +351,12 @@ def mvs_depth(images, poses, K, neighbours, planes, agg_radius: int = 2, penalty
 
     images (V,H,W) u8 grey or (V,H,W,3|4) u8; poses (V,3,4) world->camera; K (V,4);
     ``neighbours``: per view, the list of the views it is matched against (at most 16; the
-    caller's choice, e.g. the views next to it in the match graph); planes as for
-    :func:`plane_sweep`.  Views with equally long lists are swept in one call, so no list is
-    padded; a view with an empty list stays all-invalid.  ``smooth=(p1, p2[, paths])`` sweeps
+    caller's choice, e.g. the views next to it in the match graph, or
+    :func:`~.plan.plan_dense`'s); planes as for :func:`plane_sweep`, or a sequence of V such
+    arrays, one per view (``plan_dense``'s ``planes``): view r is then swept with ``planes[r]``,
+    one :func:`plane_sweep` call per view.  With one array for all, views with equally long lists
+    are swept in one call, so no list is padded; a view with an empty list stays all-invalid
+    (and its plane array may be empty).  ``smooth=(p1, p2[, paths])`` sweeps
     with semi-global smoothing as :func:`plane_sweep` does, one view at a time through one
     cost volume and one aggregated volume, so the memory is that of one view.
     ``dist`` (as for :func:`~.rectify.undistort_images`): the images were taken through the
@@ -376,7 +379,23 @@ def mvs_depth(images, poses, K, neighbours, planes, agg_radius: int = 2, penalty
     if any(not 0 <= s < V for nb in lists for s in nb):
         raise ValueError(f"a neighbour index lies outside [0, {V})")
     swept = torch.zeros((V, H, W), dtype=torch.float32, device=gpu)
-    if smooth is not None:
+    per_view = isinstance(planes, (list, tuple)) and len(planes) > 0 and all(hasattr(p, "__len__") for p in planes)
+    if per_view and len(planes) != V:
+        raise ValueError(f"planes must hold one array per view ({V}), got {len(planes)}")
+    if per_view and smooth is not None:
+        p1, p2, mask = _smooth(smooth)
+        agg_radius, penalty, uniq, min_views = _sweep_ints(agg_radius, penalty, uniq, min_views)
+        for r in range(V):
+            if lists[r]:
+                a = _sweep_inputs(cen, ps, kk, [r], [lists[r]], planes[r], p_max=256)
+                sm = _aggregate(_volume(a, agg_radius, penalty), p1, p2, mask)
+                swept[r] = _select(sm, a, uniq, min_views, False)[0][0]
+                del sm
+    elif per_view:
+        for r in range(V):
+            if lists[r]:
+                swept[r] = plane_sweep(cen, ps, kk, [r], [lists[r]], planes[r], agg_radius, penalty, uniq, min_views)[0]
+    elif smooth is not None:
         p1, p2, mask = _smooth(smooth)
         agg_radius, penalty, uniq, min_views = _sweep_ints(agg_radius, penalty, uniq, min_views)
         pl = _planes(planes, 256)

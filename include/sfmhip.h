@@ -1008,6 +1008,74 @@ int sfmhip_undistort_f32(const float* src, int V, int H, int W, const double* ca
 int sfmhip_undistort_map(const double* cam_src, const double* cam_dst, int V, int H, int W, int Ho, int Wo,
                          int32_t* map /* [V][Ho][Wo][2] */, void* stream);
 
+/* ---- V13: planning the dense stage from a sparse reconstruction (build-defined)
+ * V10 takes source lists and depth planes, V5 a box: these calls derive them from the
+ * cameras, points and observations of a reconstruction (plan.py: view selection, depth
+ * ranges, scene bounds).  The reference has no counterpart.  Restated in numpy by
+ * tests/plan_ref.py.  f64 arithmetic, one IEEE round-to-nearest step per operation in
+ * the order written, no FMA; every sum is an integer sum (integer atomics): every
+ * output is defined to the bit and does not depend on the launch geometry.  All
+ * pointers are device memory.
+ *
+ * sfmhip_obs_depth: the camera-frame depth of M observations.  poses [V][3][4] f64
+ *   world -> camera, X [N][3] f64, obs_cam / obs_pt [M] i32.  With P = poses[obs_cam[m]]
+ *   and x = X[obs_pt[m]]:
+ *     d = ((P[2][0] x0 + P[2][1] x1) + P[2][2] x2) + P[2][3];  z[m] = f32(d);
+ *   where f32(d) is not finite or not > 0 (a NaN, a point behind the camera, an f64
+ *   depth that overflows or underflows f32), z[m] = +inf: it sorts last and is not
+ *   counted.  One lane per observation.  Every index must lie in [0, V) x [0, N): the
+ *   lists live on the device, so the wrapper (plan.py) checks them on the host before
+ *   the call and raises without a launch; the kernel reads nothing out of bounds for an
+ *   index that does not (such an observation gets +inf).  M <= 2^38.
+ *
+ * sfmhip_view_pair_counts: for every pair of views, the tracks both observe and those
+ *   among them with a usable triangulation angle.  centres [V][3] f64 (the wrapper's
+ *   c_i = -((R[0][i] t0 + R[1][i] t1) + R[2][i] t2), f64 on the host); X [N][3] f64;
+ *   obs_cam [M] i32 sorted by (point, camera) with pt_off [N+1] i64, the layout of
+ *   sfmhip_ba_global*, every (camera, point) pair at most once (the wrapper removes
+ *   repeats); c2_lo = cos^2 of the largest angle, c2_hi = cos^2 of the smallest, the
+ *   largest at most 90 degrees: 0 <= c2_lo <= c2_hi <= 1, else SFMHIP_E_ARG.
+ *   For a track x seen by cameras a and b, a != b:
+ *     ra = c_a - x;  rb = c_b - x  (per component);
+ *     d = (ra0 rb0 + ra1 rb1) + ra2 rb2;
+ *     n = ((ra0 ra0 + ra1 ra1) + ra2 ra2) ((rb0 rb0 + rb1 rb1) + rb2 rb2);
+ *     good iff d > 0 and n < inf and d d >= c2_lo n and d d <= c2_hi n.
+ *   shared [V][V] i32: the tracks both views observe; good [V][V] i32: those that are
+ *   good; both symmetric with a zero diagonal, overwritten.  A point on a camera centre
+ *   (d = 0) and a point with a NaN are shared and not good by the comparisons alone;
+ *   `n < inf` makes that hold for an infinite coordinate too (inf >= inf would pass).
+ *   A track whose range in pt_off is not inside [0, M], is reversed or is longer than V
+ *   is skipped, like a camera index outside [0, V).  V <= 32767.  V = 0 is a no-op;
+ *   M = 0, N = 0 or V = 1 zero the outputs without a launch.
+ *   A track of length L has L (L - 1) / 2 pairs; the pairs, not the tracks, are dealt
+ *   out evenly over the lanes of a workgroup.  While 4 V (V - 1) bytes fit the 160 KiB of
+ *   LDS beside 3136 bytes of bookkeeping (V <= 200) every workgroup counts into upper
+ *   triangles of its own in LDS and adds its non-zero entries to global memory once;
+ *   above that, or under SFMHIP_PLAN_GLOBAL=1, every pair adds straight to global
+ *   memory.  Integer sums: both paths give the same bits.
+ *
+ * sfmhip_segmented_select: exact order statistics of f32 values per segment.  values
+ *   [M] f32, seg_off [S+1] i64 (segment s = values[seg_off[s] .. seg_off[s+1])), ranks
+ *   [S][R] i64, out [S][R] f32, R <= 8.  Total order: that of the radix key of the 32
+ *   bits, key = ~bits for a set sign bit, else bits ^ 0x80000000: -0.0 < +0.0, +inf
+ *   and the NaNs with a clear sign bit last.  out[s][r] = the value whose key has rank
+ *   ranks[s][r] (0 = smallest) among the n_s keys of segment s, its 32 bits as they are;
+ *   equal keys are equal values, so ties need no rule.  A rank outside [0, n_s) gives
+ *   the quiet NaN 0x7FC00000; a segment not inside [0, M] or reversed is empty.  One
+ *   workgroup per segment, four 8-bit most-significant-digit passes with LDS
+ *   histograms; the segment is not sorted and nothing returns to the host.
+ *
+ * A null pointer or a negative size is SFMHIP_E_ARG; shapes are checked before the
+ * empty-call no-op (M = 0 for obs_depth; S = 0 or R = 0 for the select).  Asynchronous
+ * on the stream.                                                                       */
+int sfmhip_obs_depth(const double* poses, int V, const double* X, int64_t N, const int32_t* obs_cam,
+                     const int32_t* obs_pt, int64_t M, float* z /* [M] */, void* stream);
+int sfmhip_view_pair_counts(const double* centres, int V, const double* X, int64_t N, const int32_t* obs_cam,
+                            int64_t M, const int64_t* pt_off, double c2_lo, double c2_hi,
+                            int32_t* shared /* [V][V] */, int32_t* good /* [V][V] */, void* stream);
+int sfmhip_segmented_select(const float* values, int64_t M, const int64_t* seg_off, int64_t S,
+                            const int64_t* ranks, int R, float* out /* [S][R] */, void* stream);
+
 /* ---- V11: SIFT keypoints and descriptors (build-defined) ---------------------
  * Scale-space extrema, orientation and the 128-d descriptor of V grey images, in
  * four calls.  The reference has no counterpart (it reads features from disk).
