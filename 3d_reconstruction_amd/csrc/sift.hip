@@ -343,7 +343,10 @@ __device__ __forceinline__ RecView sift_read_rec(const int32_t* r, int O) {
     k.x = __int_as_float(r[2]);
     k.y = __int_as_float(r[3]);
     k.sc = __int_as_float(r[4]);
-    k.ok = k.o >= 0 && k.o < O && k.l >= 1 && k.l <= kS;   // a record outside the contract reads nothing
+    // a record outside the contract reads nothing: octave and level in range, x, y and the scale
+    // finite and at most 2^20 in magnitude, the scale positive (a NaN fails every comparison)
+    k.ok = k.o >= 0 && k.o < O && k.l >= 1 && k.l <= kS && fabsf(k.x) <= 1048576.0f && fabsf(k.y) <= 1048576.0f &&
+           k.sc > 0.0f && k.sc <= 1048576.0f;
     return k;
 }
 

@@ -1184,8 +1184,11 @@ int sfmhip_segmented_select(const float* values, int64_t M, const int64_t* seg_o
  * border >= 1, radii in [0, 13]: otherwise SFMHIP_E_ARG, like a null
  * pointer, without touching the GPU.  V = 0 is a no-op without a launch; cap = 0
  * still counts.  An octave with H_o or W_o < 2 border + 1 holds no start sample.
- * Records handed to steps 3 and 4 must have 0 <= octave < O, 1 <= l <= S and finite
- * floats (what step 2 writes); rec, orec, the tables and pyr are device memory.
+ * Records handed to steps 3 and 4 must have 0 <= octave < O, 1 <= l <= S (l = word 1
+ * mod 256), finite x, y and sc with |x| <= 1048576, |y| <= 1048576 and 0 < sc <= 1048576
+ * (what step 2 writes).  A record outside that contract reads nothing: it yields no
+ * oriented record from step 3 (it counts 0 peaks) and an all-zero descriptor row from
+ * step 4.  rec, orec, the tables and pyr are device memory.
  * Plain asynchronous launches on the stream; scratch from the library pool.       */
 int sfmhip_sift_pyramid(const uint8_t* img, int V, int H, int W, int O, const float* taps /* [6][27] */,
                         const int32_t* radii /* HOST [6] */, float* pyr, void* stream);

@@ -1,7 +1,9 @@
 """numpy restatement of V11, the SIFT of include/sfmhip.h (sift.hip), written from
 the header text: every f32 step in the order given there, vectorised over pixels / keypoints.
 The tables (taps, radii, sig, wo, wd, cw, cs) are arguments, as they are for the kernels.
-One view at a time; records are (N, 8) int32 with the floats as their bits."""
+One view at a time; records are (N, 8) int32 with the floats as their bits.
+detect, orient and describe take an optional dict `census` and count in it the branches they take
+(tests/test_sift_census_cpu.py); it changes nothing they return."""
 import numpy as np
 
 f32 = np.float32
@@ -52,7 +54,23 @@ def flat(octs):
     return np.concatenate([g.ravel() for g in octs])
 
 
-def detect(octs, tb, border=5, contrast=0.04, edge=10.0):
+def _count(census, key, n=1):
+    if census is not None:
+        census[key] = census.get(key, 0) + int(n)
+
+
+def in_contract(rec, O):
+    """The record contract of the header: octave and level in range, x, y and the scale finite and
+    at most 2^20 in magnitude, the scale positive.  A record outside it reads nothing."""
+    o, l, _, x, y, sc = _fields(rec)
+    big = f32(1048576)
+    with np.errstate(invalid="ignore"):
+        return (o >= 0) & (o < O) & (l >= 1) & (l <= S) & (np.abs(x) <= big) & (np.abs(y) <= big) & (sc > 0) & \
+            (sc <= big)
+
+
+def detect(octs, tb, border=5, contrast=0.04, edge=10.0, census=None):
+    """census (a dict, optional) counts the branches taken: it changes nothing that is returned."""
     pre = f32(0.5 * contrast / S * 255.0)
     cthr = f32(contrast * 255.0)
     er = f32(edge)
@@ -76,6 +94,7 @@ def detect(octs, tb, border=5, contrast=0.04, edge=10.0):
                     gt &= v > n
                     lt &= v < n
         cand = np.argwhere(gt | lt)   # ascending (level, row, column)
+        _count(census, "start", cand.shape[0])
         if cand.shape[0] == 0:
             continue
         l, y, x = cand[:, 0] + 1, cand[:, 1] + border, cand[:, 2] + border
@@ -84,7 +103,7 @@ def detect(octs, tb, border=5, contrast=0.04, edge=10.0):
         conv = np.zeros(N, bool)
         fin = {k: np.zeros(N, f32) for k in ("c", "gx", "gy", "gl", "hxx", "hyy", "hxy", "ox", "oy", "ol")}
         with np.errstate(all="ignore"):
-            for _ in range(5):
+            for it in range(5):
                 act = alive & ~conv
                 c = D[l, y, x]
                 xp, xm, yp, ym, lp, lm = D[l, y, x + 1], D[l, y, x - 1], D[l, y + 1, x], D[l, y - 1, x], D[l + 1, y, x], \
@@ -118,16 +137,38 @@ def detect(octs, tb, border=5, contrast=0.04, edge=10.0):
                     (nx <= W - 1 - border)
                 alive &= ~(mv & ~inb)
                 ok = mv & inb
+                l0 = l
                 l, y, x = np.where(ok, nl, l), np.where(ok, ny, y), np.where(ok, nx, x)
+                if census is not None:
+                    lev = (nl >= 1) & (nl <= S)
+                    _count(census, "det0", (act & ~okdet).sum())
+                    _count(census, "offset_above_2^20", (act & okdet & ~cv & ~small).sum())
+                    _count(census, "conv_solve_%d" % (it + 1), now.sum())
+                    _count(census, "move", ok.sum())
+                    _count(census, "move_level", (ok & (nl != l0)).sum())
+                    _count(census, "leave_level", (mv & ~lev).sum())
+                    _count(census, "leave_rowcol", (mv & lev & ~inb).sum())
             keep = alive & conv
+            _count(census, "no_conv_after_5", (alive & ~conv).sum())
             ox, oy, ol = fin["ox"], fin["oy"], fin["ol"]
             resp = fin["c"] + f32(0.5) * ((fin["gx"] * ox + fin["gy"] * oy) + fin["gl"] * ol)
-            keep &= np.abs(resp) * f32(3) >= cthr
+            strong = np.abs(resp) * f32(3) >= cthr
             tr = fin["hxx"] + fin["hyy"]
             d2 = fin["hxx"] * fin["hyy"] - fin["hxy"] * fin["hxy"]
             e1 = er + f32(1)
-            keep &= (d2 > 0) & ((tr * tr) * er < (e1 * e1) * d2)
+            round_ = (tr * tr) * er < (e1 * e1) * d2
+            _count(census, "contrast", (keep & ~strong).sum())
+            _count(census, "d2", (keep & strong & ~(d2 > 0)).sum())
+            _count(census, "edge", (keep & strong & (d2 > 0) & ~round_).sum())
+            _count(census, "edge_both_sides_equal", (keep & strong & (d2 > 0) & ((tr * tr) * er == (e1 * e1) * d2)).sum())
+            keep &= strong & (d2 > 0) & round_
         l, y, x, ox, oy, ol, resp = (a[keep] for a in (l, y, x, ox, oy, ol, resp))
+        if census is not None:
+            _count(census, "scale_ol>=0", (ol >= 0).sum())
+            _count(census, "scale_ol<0", (ol < 0).sum())
+            for ll in range(1, S + 1):
+                _count(census, "kept_level_%d" % ll, (l == ll).sum())
+            _count(census, "records", l.shape[0])
         s0 = sig[l]
         sc = np.where(ol >= 0, s0 + ol * (sig[l + 1] - s0), s0 + ol * (s0 - sig[l - 1])).astype(f32)
         fx, fy, po = x.astype(f32) + ox, y.astype(f32) + oy, f32(1 << o)
@@ -188,8 +229,13 @@ def _patches(octs, rec, n, pos):
     return P
 
 
-def orient(octs, rec, tb):
-    """(N, 8) records -> (M, 8) oriented records (word 1 = level | q << 8)."""
+def orient(octs, rec, tb, census=None):
+    """(N, 8) records -> (M, 8) oriented records (word 1 = level | q << 8).  A record outside the
+    contract gives none."""
+    good = in_contract(rec, len(octs))
+    _count(census, "orient_records", rec.shape[0])
+    _count(census, "orient_out_of_contract", (~good).sum())
+    rec = rec[good]
     N = rec.shape[0]
     if N == 0:
         return np.zeros((0, 8), np.int32)
@@ -219,16 +265,34 @@ def orient(octs, rec, tb):
     peak = (hs > lf) & (hs > rt) & (hs >= f32(0.8) * M)
     with np.errstate(all="ignore"):
         bf = (np.arange(36).astype(f32)[None] + f32(0.5)) + f32(0.5) * (lf - rt) / ((lf - f32(2) * hs) + rt)
-        q = np.where(peak, np.rint((bf * f32(1024)) / f32(36)), 0).astype(np.int64) % 1024
+        qr = np.where(peak, np.rint((bf * f32(1024)) / f32(36)), 0).astype(np.int64)
+        q = qr % 1024
+    if census is not None:
+        npk = peak.sum(1)
+        for k in range(5):
+            _count(census, "peaks_%d" % k, (npk == k).sum())
+        _count(census, "peaks_above_4", (npk > 4).sum())
+        _count(census, "peak_in_bin_0", peak[:, 0].sum())
+        _count(census, "peak_in_bin_35", peak[:, 35].sum())
+        _count(census, "q_wrap", (peak & (qr != q)).sum())
+        _count(census, "hist_term_at_bound", (w * f32(1024) >= f32(4194304)).sum())
+        _count(census, "oriented", np.minimum(npk, 4).sum())
     sel = np.argwhere(peak & (np.cumsum(peak, 1) <= 4))   # input order, then ascending bin
     out = rec[sel[:, 0]].copy()
     out[:, 1] = (out[:, 1] & 0xff) | (q[sel[:, 0], sel[:, 1]] << 8).astype(np.int32)
     return out
 
 
-def describe(octs, orec, tb):
-    """(M, 8) oriented records -> (M, 128) u8."""
+def describe(octs, orec, tb, census=None):
+    """(M, 8) oriented records -> (M, 128) u8.  The row of a record outside the contract is zero."""
+    good = in_contract(orec, len(octs))
+    if not good.all():
+        _count(census, "describe_out_of_contract", (~good).sum())
+        out = np.zeros((orec.shape[0], 128), np.uint8)
+        out[good] = describe(octs, orec[good], tb, census)
+        return out
     M = orec.shape[0]
+    _count(census, "describe_rows", M)
     if M == 0:
         return np.zeros((0, 128), np.uint8)
     _, _, q, x, y, sc = _fields(orec)
@@ -275,7 +339,10 @@ def describe(octs, orec, tb):
         e = np.minimum(d / n[:, None], f32(0.2))
         e = np.where(ok[:, None], e, f32(0))
         n2 = norm(e)
-        r = np.minimum(np.rint(f32(512) * (e / n2[:, None])), f32(255))
+        r = np.rint(f32(512) * (e / n2[:, None]))
+        _count(census, "zero_norm", (~ok).sum())
+        _count(census, "entry_clamped_255", (ok[:, None] & (r > f32(255))).sum())
+        r = np.minimum(r, f32(255))
     return np.where(ok[:, None], r, 0).astype(np.uint8)
 
 
