@@ -146,7 +146,11 @@ __global__ __launch_bounds__(256) void icp_reduce_kernel(IcpArgs A) {
 #pragma unroll
                                     for (int a = 0; a < 3; ++a)
                                         cw[a] = (P[a] * cr[0] + P[4 + a] * cr[1]) + P[8 + a] * cr[2];
-                                    const float dotv = (cw[0] * nm[0] + cw[1] * nm[1]) + cw[2] * nm[2];
+                                    const float dotr = (cw[0] * nm[0] + cw[1] * nm[1]) + cw[2] * nm[2];
+                                    // bv x a points towards the camera iff fx fy > 0: a mirrored
+                                    // frame (one focal length negative) turns it round
+                                    const bool flip = (K[0] < 0.f) != (K[1] < 0.f);
+                                    const float dotv = flip ? -dotr : dotr;
                                     const float cc = (cw[0] * cw[0] + cw[1] * cw[1]) + cw[2] * cw[2];
                                     acc = dotv > 0.f && dotv * dotv >= A.cos2 * cc;
                                 }

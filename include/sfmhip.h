@@ -790,9 +790,14 @@ int sfmhip_tsdf_raycast(const float* T, const float* Wt, const uint32_t* C /* nu
  *   the depth test, else reject.  With pc' of the right and pc" of the lower
  *   neighbour (step 1's formula): a = pc' - pc, bv = pc" - pc,
  *   c = bv x a = (bv_y a_z - bv_z a_y, bv_z a_x - bv_x a_z, bv_x a_y - bv_y a_x)
- *   (two products and one subtraction each; it points towards the camera),
- *   cw_a = (R0a c0 + R1a c1) + R2a c2,  dotv = (cw_x nm_x + cw_y nm_y) + cw_z nm_z,
- *   cc = (cw_x cw_x + cw_y cw_y) + cw_z cw_z; accept iff dotv > 0 and
+ *   (two products and one subtraction each),
+ *   cw_a = (R0a c0 + R1a c1) + R2a c2,  dotr = (cw_x nm_x + cw_y nm_y) + cw_z nm_z,
+ *   cc = (cw_x cw_x + cw_y cw_y) + cw_z cw_z.  In camera coordinates c points
+ *   towards the camera iff fx fy > 0; a mirrored frame (exactly one of fx, fy
+ *   negative, which V5 and V8 accept) turns it round, so
+ *   dotv = -dotr when (fx < 0) != (fy < 0), else dotr: an exact sign change, cc is
+ *   the same either way.  The sign of det R does not enter: cw = R^T c is c in
+ *   world coordinates for any orthogonal R.  Accept iff dotv > 0 and
  *   dotv dotv >= cos2 cc.
  * 6 Row.  r = (nm_x e_x + nm_y e_y) + nm_z e_z;  J = (pw x nm, nm), six f32, the
  *   cross product written as in step 5.

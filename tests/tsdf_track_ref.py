@@ -106,6 +106,8 @@ def rows_one_view(depth, Kf, pose, depth_m, normals_m, pose_m, Km, dist2, cos2, 
             bv = backproject(vv + 1, uu) - pc
             cw = _rot_t(P[:, :3], _cross(bv, a))
             dotv = (cw[:, 0] * nm[:, 0] + cw[:, 1] * nm[:, 1]) + cw[:, 2] * nm[:, 2]
+            if (Kf[0] < 0) != (Kf[1] < 0):   # a mirrored frame: bv x a points away from the camera
+                dotv = -dotv
             cc = (cw[:, 0] * cw[:, 0] + cw[:, 1] * cw[:, 1]) + cw[:, 2] * cw[:, 2]
             ok = (dotv > 0) & (dotv * dotv >= cos2 * cc)
             vv, uu, pw, nm, e = vv[ok], uu[ok], pw[ok], nm[ok], e[ok]
