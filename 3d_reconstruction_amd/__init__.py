@@ -29,12 +29,13 @@ from .plan import (DensePlan, cubic_grid, dense_inputs_from_reconstruction, obs_
                    segmented_select, select_sources, view_depth_ranges, view_pair_counts)
 from .features import (sift, sift_describe, sift_detect, sift_orient, sift_pyramid,  # noqa: F401
                        sift_tables)
-from . import bow, features, mesh, mvs, pipeline, plan, reconstruct, rectify, tracks, verify  # noqa: F401,E402
+from . import bow, features, mesh, mvs, pipeline, plan, reconstruct, rectify, tracks, twoview, verify  # noqa: F401,E402
 from .mesh import write_ply  # noqa: F401
 from .bow import kmeans  # noqa: F401
 from .reconstruct import triangulate  # noqa: F401
-from .tracks import MatchGraph, bfs_tracks  # noqa: F401
-from .verify import RANSAC, SOLVEPNP_ITERATIVE, findEssentialMat, recoverPose, solvePnPRansac  # noqa: F401
+from .tracks import MatchGraph, bfs_tracks, with_initial_pair  # noqa: F401
+from .verify import RANSAC, SOLVEPNP_ITERATIVE, findEssentialMat, findHomography, recoverPose, solvePnPRansac  # noqa: F401
+from .twoview import classify_pairs, select_initial_pair  # noqa: F401
 from .dist import RcclComm, match_all_pairs_sharded  # noqa: F401
 
 __version__ = "0.1.0"

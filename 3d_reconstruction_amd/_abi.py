@@ -147,6 +147,8 @@ SIGNATURES = {
     "sfmhip_sift_describe": [_p, _i32, _i32, _i32, _i32, _p, _p, _i32, _p, _p, _p, _p, _p],
     "sfmhip_find_essential": [_p, _p, _p, _i32, _p, _f64, _f64, _i32, _p, _p, _p, _p, _p, _p, _p],
     "sfmhip_recover_pose": [_p, _i64, _p, _p, _p, _i32, _p, _p, _f64, _p, _p, _p, _p, _p],
+    "sfmhip_find_homography": [_p, _p, _p, _i32, _f64, _f64, _i32, _p, _p, _p, _p, _p, _p],
+    "sfmhip_pair_stats": [_p, _p, _p, _i32, _i64, _p, _p, _p, _f64, _f64, _p, _p, _p, _p, _p, _p, _p],
     "sfmhip_pnp_ransac": [_p, _p, _p, _i32, _p, _i32, _f64, _f64, _p, _p, _p, _p, _p, _p, _p, _p],
     "sfmhip_render_train": [_p, _i32, _i32, _i32, _p, _p, _i32, _p, _p, _p, _p, _i64, _i32, _p, _p, _p, _p, _p],
     "sfmhip_adam_step": [_p, _p, _p, _p, _i64, _f64, _f64, _f64, _f64, _i64, _i32, _p],

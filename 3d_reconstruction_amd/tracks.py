@@ -116,6 +116,18 @@ def bfs_tracks(connection, start: int, n_kpts, match_fn, verify=None, min_raw: i
     return queue[1:], all_matches
 
 
+def with_initial_pair(connection, i: int, j: int):
+    """A copy of the connection graph with ``j`` moved to the front of ``connection[i]`` (added
+    there if absent), so that ``bfs_tracks(conn, start=i, ...)`` examines (i, j) first and
+    incremental_sfm fixes its frame and scale on that pair (twoview.select_initial_pair)."""
+    i, j = int(i), int(j)
+    if not 0 <= i < len(connection) or not 0 <= j < len(connection) or i == j:
+        raise ValueError(f"({i}, {j}) is not a pair of two of the graph's {len(connection)} images")
+    conn = [[int(v) for v in row] for row in connection]
+    conn[i] = [j] + [v for v in conn[i] if v != j]
+    return conn
+
+
 def save_outputs(out_dir: str, img_pairs, all_matches) -> None:
     """matching.py:188-189 formats: img_pairs.npy (P,2), all_matches.npy object (P,3)."""
     import os

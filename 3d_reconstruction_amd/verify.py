@@ -11,9 +11,13 @@
   ``verify`` callback of :func:`tracks.bfs_tracks`; :class:`EssentialVerifier`
   batches it over every candidate pair of the BoW connection graph.
 
-Semantics follow OpenCV 4.x (restated in oracle/ransac.py; parity unpinned:
+* :func:`findHomography` / :func:`find_homography_batched` — ``cv2.findHomography(src, dst,
+  cv2.RANSAC, 3)`` (not called by the reference; twoview.py compares its support with the essential
+  matrix's), and :func:`pair_stats_batched`, the parallax and image coverage of a pair.
+
+Semantics follow OpenCV 4.x (restated in oracle/ransac.py and tests/homog_ref.py; parity unpinned:
 cv2 is not installed here).  Every call runs ``sfmhip_find_essential`` /
-``sfmhip_recover_pose``; there is no CPU path.
+``sfmhip_recover_pose`` / ``sfmhip_find_homography`` / ``sfmhip_pair_stats``; there is no CPU path.
 """
 from __future__ import annotations
 
@@ -129,6 +133,76 @@ def recoverPose(E, points1, points2, cameraMatrix, R=None, t=None, mask=None, di
     r = recover_pose_batched(Ed, a, b, of, _cam(cameraMatrix), mk, distanceThresh)
     return (int(r["n_good"][0]), r["R"][0].cpu().numpy(), r["t"][0].cpu().numpy().reshape(3, 1),
             r["mask"].cpu().numpy().reshape(-1, 1))
+
+
+def find_homography_batched(pts0: torch.Tensor, pts1: torch.Tensor, offsets: torch.Tensor, threshold: float = 3.0,
+                            max_iters: int = 2000, confidence: float = 0.995) -> dict:
+    """cv2.findHomography (RANSAC) over many pairs in one launch (one workgroup per pair), in
+    :func:`find_essential_batched`'s packed layout: pts0 -> pts1 in pixels, no camera.  Returns
+    device tensors H (P,3,3) f64 with H[2,2] = 1 (zeros where ok = 0), ok (P,), mask (N,) u8 0/1,
+    n_inliers (P,), iters (P,)."""
+    p0 = dev(pts0, torch.float64)
+    p1 = dev(pts1, torch.float64)
+    of = dev(offsets, torch.int64)
+    P = of.numel() - 1
+    N = p0.shape[0]
+    d = p0.device
+    out = dict(H=torch.zeros((P, 3, 3), dtype=torch.float64, device=d),
+               ok=torch.zeros(P, dtype=torch.int32, device=d),
+               mask=torch.zeros(N, dtype=torch.uint8, device=d),
+               n_inliers=torch.zeros(P, dtype=torch.int32, device=d),
+               iters=torch.zeros(P, dtype=torch.int32, device=d))
+    if N == 0:      # nothing to launch on: every pair is empty, and an empty tensor has no address
+        return out
+    call("sfmhip_find_homography", ptr(p0), ptr(p1), ptr(of), P, float(threshold), float(confidence), int(max_iters),
+         ptr(out["H"]), ptr(out["ok"]), ptr(out["mask"]), ptr(out["n_inliers"]), ptr(out["iters"]), stream_ptr())
+    return out
+
+
+def findHomography(srcPoints, dstPoints, method: int = RANSAC, ransacReprojThreshold: float = 3.0, mask=None,
+                   maxIters: int = 2000, confidence: float = 0.995):
+    """cv2.findHomography (RANSAC) -> (H (3,3) f64, mask (n,1) u8) or (None, None).  Without
+    OpenCV's Levenberg-Marquardt polish of the refitted H."""
+    if method != RANSAC:
+        raise NotImplementedError("only method=cv2.RANSAC is implemented")
+    p0 = np.asarray(srcPoints, np.float64).reshape(-1, 2)
+    p1 = np.asarray(dstPoints, np.float64).reshape(-1, 2)
+    if len(p0) != len(p1):
+        raise ValueError("srcPoints and dstPoints must have the same number of points")
+    a, b, of = pack_pairs([p0], [p1])
+    r = find_homography_batched(a, b, of, ransacReprojThreshold, maxIters, confidence)
+    if not int(r["ok"][0]):
+        return None, None
+    return r["H"][0].cpu().numpy(), r["mask"].cpu().numpy().reshape(-1, 1)
+
+
+def pair_stats_batched(pts0: torch.Tensor, pts1: torch.Tensor, offsets: torch.Tensor, mask: torch.Tensor,
+                       R: torch.Tensor, cam, size) -> dict:
+    """Parallax and image coverage of the correspondences ``mask`` selects, per pair
+    (sfmhip_pair_stats): R (P,3,3) the relative rotation, cam (P,4) or (4,), size = (width, height)
+    of both images.  Returns device tensors cosang (N,) f64 (the cosine of the angle between the rays
+    K^-1 x0 and R^T K^-1 x1; 2.0 on unselected rows), cover (P,2) int64 (the bits of the 8x8 occupancy
+    words of image 0 / 1), n_sel (P,) and median (P,) f32: the lower median of a pair's selected
+    cosines rounded to float, an exact order statistic (sfmhip_segmented_select)."""
+    p0 = dev(pts0, torch.float64)
+    p1 = dev(pts1, torch.float64)
+    of = dev(offsets, torch.int64)
+    P = of.numel() - 1
+    N = p0.shape[0]
+    mk = dev(mask, torch.uint8)
+    Rt = dev(R, torch.float64).reshape(P, 9)
+    c = _cam_rows(cam, P)
+    d = p0.device
+    out = dict(cosang=torch.empty(N, dtype=torch.float64, device=d),
+               cover=torch.zeros((P, 2), dtype=torch.int64, device=d),
+               n_sel=torch.zeros(P, dtype=torch.int32, device=d),
+               median=torch.empty(P, dtype=torch.float32, device=d))
+    work = torch.empty(max(N, 1), dtype=torch.float32, device=d)
+    rank = torch.empty(max(P, 1), dtype=torch.int64, device=d)
+    call("sfmhip_pair_stats", ptr(p0), ptr(p1), ptr(of), P, N, ptr(mk), ptr(Rt), ptr(c), float(size[0]),
+         float(size[1]), ptr(out["cosang"]), ptr(work), ptr(rank), ptr(out["cover"]), ptr(out["n_sel"]),
+         ptr(out["median"]), stream_ptr())
+    return out
 
 
 def essential_inliers_batched(pts0_list, pts1_list, K, prob: float = 0.999, threshold: float = 1.0):

@@ -1236,6 +1236,36 @@ int sfmhip_recover_pose(const double* E, int64_t e_stride, const double* pts0, c
                         const uint8_t* mask_in, double distance_thresh, double* R, double* t,
                         uint8_t* mask_out, int32_t* n_good, void* stream);
 
+/* cv2.findHomography(src, dst, cv2.RANSAC, ransacReprojThreshold=3, maxIters=2000,
+ * confidence=0.995), batched over image pairs in sfmhip_find_essential's packed
+ * layout (pixels; no camera): cv::RNG(-1) 4-point samples, checkSubset (no three
+ * points collinear in either image, every triple keeps its orientation; a
+ * rejected sample is one iteration without a model), Hartley-normalised DLT,
+ * forward transfer error (float) <= threshold^2, a model replaces the best iff
+ * count > max(best, 3), RANSACUpdateNumIters; the final H is the DLT over the
+ * winning model's inliers (no Levenberg-Marquardt polish).
+ * Out: H [n_pairs][9] (row-major, H[8] = 1; zeros where ok = 0), ok, mask [N]
+ * u8 0/1 (the winning sample model's), n_inliers, iters (samples drawn).
+ * All pointers are device memory.                                            */
+int sfmhip_find_homography(const double* pts0, const double* pts1, const int64_t* offsets, int n_pairs,
+                           double threshold, double confidence, int max_iters, double* H, int32_t* ok,
+                           uint8_t* mask, int32_t* n_inliers, int32_t* iters, void* stream);
+
+/* Parallax and image coverage of the correspondences that mask [N] u8 selects,
+ * per pair (R [n_pairs][9] the relative rotation, cam [n_pairs][4] = fx, fy,
+ * cx, cy; both images width x height pixels).  Out: cosang [N] f64, the cosine
+ * of the angle between the rays K^-1 x0 and R^T K^-1 x1 (2.0 on unselected
+ * rows); cover [n_pairs][2] u64, bit 8 floor(8y/height) + floor(8x/width) set
+ * for every selected point inside [0, width) x [0, height) of image 0 / 1;
+ * n_sel [n_pairs], the selected rows; median [n_pairs] f32, the lower median of
+ * the pair's selected cosines rounded to float, by sfmhip_segmented_select
+ * (2.0 when none is selected, NaN for an empty pair).  work [N] f32 and
+ * rank_work [n_pairs] int64 are scratch.  All pointers are device memory.     */
+int sfmhip_pair_stats(const double* pts0, const double* pts1, const int64_t* offsets, int n_pairs,
+                      int64_t n_points, const uint8_t* mask, const double* R, const double* cam,
+                      double width, double height, double* cosang, float* work, int64_t* rank_work,
+                      uint64_t* cover, int32_t* n_sel, float* median, void* stream);
+
 /* cv2.solvePnPRansac(X, pts1, K, zeros(5,1), cv2.SOLVEPNP_ITERATIVE) at
  * sfm.py:116 (iterationsCount 100, reprojectionError 8, confidence 0.99):
  * points converted to float, cv::RNG(-1) 5-point samples solved by EPnP,
