@@ -18,7 +18,7 @@ from .geometry import (Rodrigues, ba_sparse, calculate_reprojection_error,  # no
                        residual_jacobian_batched, triangulatePoints, triangulate_batched, ba_solve_batched,
                        least_squares_ba, ba_global_structure, ba_global_linearize, ba_global_schur_matvec,
                        bundle_adjust, ba_loss_weight, ba_calib_linearize, ba_calib_matvec, undistort_points,
-                       undistortPoints)
+                       undistortPoints, triangulate_tracks)
 from .voxel import (MASK_PLENOXEL, MASK_SDF, VoxelGrid, icp_normal_equations, icp_track, tsdf_block_table,  # noqa: F401,E501
                     tsdf_cull_stats, tsdf_integrate, tsdf_extract_surface, tsdf_integrate_colour, tsdf_layer_cost,
                     tsdf_layer_stats, tsdf_raycast, tsdf_track, voxel_traversal)
@@ -32,7 +32,7 @@ from .features import (sift, sift_describe, sift_detect, sift_orient, sift_pyram
 from . import bow, features, mesh, mvs, pipeline, plan, reconstruct, rectify, tracks, twoview, verify  # noqa: F401,E402
 from .mesh import write_ply  # noqa: F401
 from .bow import kmeans  # noqa: F401
-from .reconstruct import triangulate  # noqa: F401
+from .reconstruct import retriangulate, triangulate  # noqa: F401
 from .tracks import MatchGraph, bfs_tracks, with_initial_pair  # noqa: F401
 from .verify import RANSAC, SOLVEPNP_ITERATIVE, findEssentialMat, findHomography, recoverPose, solvePnPRansac  # noqa: F401
 from .twoview import classify_pairs, select_initial_pair  # noqa: F401

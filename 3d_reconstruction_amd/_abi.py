@@ -84,6 +84,8 @@ SIGNATURES = {
     "sfmhip_track_interlace": [_p, _i64, _p, _i64, _p, _p, _i64, _p],
     "sfmhip_track_merge": [_p, _i64, _p, _i64, _p, _p, _i64, _p, _p],
     "sfmhip_triangulate_dlt": [_p, _p, _p, _p, _i64, _p, _p],
+    "sfmhip_triangulate_tracks": [_p, _p, _i32, _p, _i64, _p, _p, _i64, _p, _f64, _f64, _i32, _i32, _p, _p, _p, _p, _p,
+                                  _p, _p, _p],
     "sfmhip_reproj_residual": [_p, _p, _p, _p, _p, _i64, _p, _p],
     "sfmhip_reproj_residual_host": [_p, _p, _p, _p, _i64, _p, _p],
     "sfmhip_reproj_fd_jacobian": [_p, _p, _p, _p, _p, _i32, _i64, _p, _p, _p, _p],

@@ -639,3 +639,117 @@ def bundle_adjust(cam, K, X, obs_cam, obs_pt, pts2d, cam_fixed=None, gtol: float
     return _BundleResult(cam=camt.cpu().numpy(), X=Xt.cpu().numpy(), cost0=cost[0], cost=cost[1],
                          status=int(info[0]), nit=int(info[1]), n_accept=int(info[2]), n_cg=int(info[3]),
                          loss=loss, f_scale=f_scale, _res2=res2, _order=d["order"])
+
+
+# ---------------------------------------------------------------------------
+# S2b: robust N-view triangulation of tracks (triangulate.hip; build-defined)
+TRI_STATUS = {0: "ok", 1: "fewer than two distinct cameras", 2: "no hypothesis survived",
+              3: "final angle too small", 4: "fit failed"}
+
+
+def triangulate_tracks(poses, K, obs_cam, obs_pt, pts2d, n_tracks=None, dist=None, reproj_px: float = 4.0,
+                       min_angle: float = 1.5, max_hyp: int = 256, refine_iters: int = 3, cam_group=None):
+    """Every track's 3D point from all of its observations, some of which may be wrong matches
+    (``sfmhip_triangulate_tracks``, include/sfmhip.h S2b: two-view hypotheses scored against the
+    whole track, a Gauss-Newton fit to the winner's inliers, one re-classification and a refit).
+
+    ``poses`` (C,3,4) world -> camera, or a list with ``None`` for an unregistered camera, whose
+    observations are dropped; ``K`` (3,3) or (C,3,3) with zero skew; observation m says camera
+    obs_cam[m] saw track obs_pt[m] at pts2d[m], in any order (the sort is
+    :func:`ba_global_structure`'s; a repeated (track, camera) pair is legal).  ``n_tracks``
+    defaults to the largest track index + 1.  ``dist`` = (k1, k2), or one row per intrinsics
+    group as :func:`bundle_adjust` reports it with ``cam_group`` (C,) as there (one row per
+    camera without it): the observations first pass through :func:`undistort_points`, and
+    residuals are then in undistorted pixels.  An observation is an inlier within ``reproj_px``
+    pixels; ``min_angle`` (degrees) is the smallest triangulation angle, ``max_hyp`` the most
+    hypotheses per track, ``refine_iters`` the Gauss-Newton steps per fit.
+
+    Returns an object with ``X`` (N,3; NaN unless OK), ``status`` (N,; TRI_STATUS), ``ok`` (N,) bool,
+    ``n_inliers`` (N,), and ``inlier`` (M,) bool and ``residual`` (M,; pixels under X, NaN where the
+    track is not OK or the observation was dropped) in the caller's order, and ``n_hyp``, the
+    hypotheses scored.  Index and shape errors raise ValueError before any launch."""
+    poses = list(poses)
+    C = len(poses)
+    registered = np.array([p is not None for p in poses], bool)
+    P = np.zeros((C, 3, 4))
+    for c in np.nonzero(registered)[0]:
+        Pc = np.asarray(poses[c], np.float64)
+        if Pc.shape != (3, 4):
+            raise ValueError(f"pose {c} must be (3, 4), got {Pc.shape}")
+        P[c] = Pc
+    K = np.asarray(K, np.float64)
+    if K.shape == (3, 3):
+        K = np.broadcast_to(K, (C, 3, 3))
+    if K.shape != (C, 3, 3):
+        raise ValueError("K must be (3, 3) or (C, 3, 3)")
+    if C and np.any(K[:, 0, 1] != 0):
+        raise ValueError("the camera matrices must have zero skew")
+    obs_cam = np.asarray(obs_cam).ravel()
+    obs_pt = np.asarray(obs_pt).ravel()
+    pts2d = np.asarray(pts2d, np.float64)
+    M = len(obs_cam)
+    if len(obs_pt) != M or pts2d.size != 2 * M:
+        raise ValueError("obs_cam, obs_pt and pts2d must have one row per observation")
+    pts2d = pts2d.reshape(M, 2)
+    if M and not (np.issubdtype(obs_cam.dtype, np.integer) and np.issubdtype(obs_pt.dtype, np.integer)):
+        raise ValueError("obs_cam and obs_pt must be integers")
+    obs_cam, obs_pt = obs_cam.astype(np.int64), obs_pt.astype(np.int64)
+    if n_tracks is None:
+        n_tracks = int(obs_pt.max()) + 1 if M else 0
+    N = int(n_tracks)
+    if N < 0 or N > 2 ** 31 - 1:
+        raise ValueError("n_tracks must be in [0, 2^31)")
+    if M and (obs_cam.min() < 0 or obs_cam.max() >= C):
+        raise ValueError("obs_cam entries must lie in [0, C)")
+    if M and (obs_pt.min() < 0 or obs_pt.max() >= N):
+        raise ValueError("obs_pt entries must lie in [0, n_tracks)")
+    if not (np.isfinite(reproj_px) and reproj_px > 0):
+        raise ValueError("reproj_px must be finite and positive")
+    if not (np.isfinite(min_angle) and 0 <= min_angle < 90):
+        raise ValueError("min_angle must be in [0, 90) degrees")
+    if int(max_hyp) < 1 or int(max_hyp) > 1 << 20:
+        raise ValueError("max_hyp must be in [1, 2^20]")
+    if int(refine_iters) < 0:
+        raise ValueError("refine_iters must not be negative")
+    grp = None
+    if dist is not None:
+        dist = _calib_dist(dist)
+        grp = np.zeros(C, np.int64) if len(dist) == 1 else (np.arange(C) if cam_group is None
+                                                            else np.asarray(cam_group).astype(np.int64).ravel())
+        if grp.shape != (C,) or (C and (grp.min() < 0 or grp.max() >= len(dist))):
+            raise ValueError(f"dist has {len(dist)} rows; cam_group must map every camera to one of them")
+    d = require_gpu()
+    use = np.nonzero(registered[obs_cam])[0] if M else np.zeros(0, np.int64)
+    oc, ot, uv = obs_cam[use], obs_pt[use], np.ascontiguousarray(pts2d[use])
+    if dist is not None and len(oc):
+        for c in np.unique(oc):
+            sel = oc == c
+            uv[sel] = undistort_points(uv[sel], K[c], dist[grp[c]])
+    order, pt_off, _, _ = ba_global_structure(oc, ot, C, N)
+    Mu = len(oc)
+    cos_min = math.cos(math.radians(float(min_angle)))           # on the host: the device uses no transcendentals
+    cam4 = np.ascontiguousarray(np.stack([K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]], 1)) if C else np.zeros((0, 4))
+    track_order = np.argsort(-np.diff(pt_off), kind="stable").astype(np.int32)   # long tracks first: like trip counts
+    Xt = torch.empty((N, 3), dtype=torch.float64, device=d)
+    st = torch.empty((N,), dtype=torch.int32, device=d)
+    ni = torch.empty((N,), dtype=torch.int32, device=d)
+    inl = torch.empty((Mu,), dtype=torch.uint8, device=d)
+    res = torch.empty((Mu,), dtype=torch.float64, device=d)
+    n_hyp = ctypes.c_int64(0)
+    # the inputs stay referenced until the call returns
+    Pt, camt = (dev(P, torch.float64), dev(cam4, torch.float64)) if C else (None, None)
+    offt = dev(pt_off, torch.int64)
+    oct_, uvt = (dev(oc[order].astype(np.int32), torch.int32),
+                 dev(np.ascontiguousarray(uv[order]), torch.float64)) if Mu else (None, None)
+    ordt = dev(track_order, torch.int32) if N else None
+    call("sfmhip_triangulate_tracks", ptr(Pt), ptr(camt), C, ptr(offt), N, ptr(oct_), ptr(uvt), Mu, ptr(ordt),
+         float(reproj_px), cos_min, int(max_hyp), int(refine_iters), ptr(Xt) if N else None, ptr(st) if N else None,
+         ptr(ni) if N else None, ptr(inl) if Mu else None, ptr(res) if Mu else None, ctypes.addressof(n_hyp), None,
+         stream_ptr())
+    inlier = np.zeros(M, bool)
+    residual = np.full(M, np.nan)
+    inlier[use[order]] = inl.cpu().numpy().astype(bool)
+    residual[use[order]] = res.cpu().numpy()
+    status = st.cpu().numpy()
+    return SimpleNamespace(X=Xt.cpu().numpy(), status=status, ok=status == 0, n_inliers=ni.cpu().numpy(),
+                           inlier=inlier, residual=residual, n_hyp=int(n_hyp.value))

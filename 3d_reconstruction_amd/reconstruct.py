@@ -218,6 +218,75 @@ def global_refine(cameras, all_point3ds, img_pairs, all_matches, all_points, foc
     return res, len(oc)
 
 
+def track_candidates(cameras, img_pairs, all_matches, all_points, n_tracks: int):
+    """The observations the match lists hold of the registered cameras, as :func:`global_refine`
+    collects them but with the tracks that have no point included: for pair (i, j), keypoints
+    idx0[w] of image i and idx1[w] of image j observe track idx3d[w], once per (camera, track,
+    keypoint).  Returns (cand (M,3) int64 = camera, track, keypoint, sorted; pts2d (M,2) f64)."""
+    cand = []
+    for index, (i, j) in enumerate(img_pairs):
+        idx0, idx1, idx3d = (np.asarray(a, np.int64) for a in all_matches[index])
+        for c, kp in ((i, idx0), (j, idx1)):
+            if cameras[c] is not None:
+                ok = (idx3d >= 0) & (idx3d < n_tracks)
+                cand.append(np.stack([np.full(int(ok.sum()), c, np.int64), idx3d[ok], kp[ok]], 1))
+    cand = np.unique(np.concatenate(cand), axis=0) if cand else np.zeros((0, 3), np.int64)
+    uv = np.zeros((len(cand), 2))
+    for c in np.unique(cand[:, 0]):
+        sel = cand[:, 0] == c
+        uv[sel] = np.asarray(all_points[c], np.float64)[cand[sel, 2]]
+    return cand, uv
+
+
+def retriangulate(cameras, all_point3ds, img_pairs, all_matches, all_points, focal: float = FOCAL, all_colors=None,
+                  mode: str = "missing", **knobs):
+    """Re-estimate the tracks of an :func:`incremental_sfm` / :func:`global_refine` state from all
+    of their observations under the current cameras, in place (geometry.triangulate_tracks; not
+    part of the reference, which gives a track the point of the pair it is first seen in).
+
+    Candidates are :func:`track_candidates`: every keypoint of a registered camera observes its
+    track, tracks without a point included.  ``mode="missing"``: only tracks that are ``None`` in
+    ``all_point3ds[0]`` receive a point (tracks the first pair rejected, or that a polish
+    dropped); ``mode="all"``: every track whose status is OK is replaced as well (after the
+    calibration changed, say).  A track that fails keeps what it had.  A newly created track
+    takes the colour of the keypoint of its first inlier observation when ``all_colors`` is
+    given.  ``knobs``: dist, reproj_px, min_angle, max_hyp, refine_iters of triangulate_tracks, and
+    ``K`` (3,3), which replaces the camera matrix built from ``focal`` (principal point 0) — after
+    ``global_refine(..., refine_intrinsics=...)`` pass its result's ``K[0]`` and ``dist``.
+
+    Returns triangulate_tracks' result with ``obs_cam``, ``obs_track``, ``pts2d`` (the candidate
+    list its ``inlier`` and ``residual`` refer to), ``obs_kp``, ``n_new`` and ``n_replaced`` added."""
+    from .geometry import triangulate_tracks
+    if mode not in ("missing", "all"):
+        raise ValueError(f"mode must be 'missing' or 'all', got {mode!r}")
+    n_tr = len(all_point3ds[0])
+    K = knobs.pop("K", None)
+    K = np.array([[focal, 0, 0], [0, focal, 0], [0, 0, 1.0]]) if K is None else np.asarray(K, np.float64)
+    if K.shape != (3, 3):
+        raise ValueError("K must be (3, 3): the one camera all images share")
+    cand, uv = track_candidates(cameras, img_pairs, all_matches, all_points, n_tr)
+    oc, ot, kp = cand[:, 0], cand[:, 1], cand[:, 2]
+    res = triangulate_tracks(cameras, K, oc, ot, uv, n_tracks=n_tr, **knobs)
+    had = np.array([p is not None for p in all_point3ds[0]], bool)
+    first = np.full(n_tr, -1, np.int64)          # the first inlier observation of every track
+    idx = np.nonzero(res.inlier)[0]
+    first[ot[idx[::-1]]] = idx[::-1]
+    n_new = n_replaced = 0
+    for t in np.nonzero(res.ok)[0]:
+        if had[t] and mode != "all":
+            continue
+        all_point3ds[0][t] = res.X[t].copy()
+        if had[t]:
+            n_replaced += 1
+        else:
+            n_new += 1
+            if all_colors is not None and first[t] >= 0:
+                all_point3ds[1][t] = all_colors[oc[first[t]]][kp[first[t]]]
+    res.obs_cam, res.obs_track, res.obs_kp, res.pts2d = oc, ot, kp, uv
+    res.n_new, res.n_replaced = n_new, n_replaced
+    return res
+
+
 def save_sfm_outputs(out_dir: str, img_list, cameras, all_point3ds) -> None:
     """sfm.py:133-146 formats: reconstructed_img.txt, cameras_extrinsic.npy, points_3d.npy."""
     import os

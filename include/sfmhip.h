@@ -255,6 +255,90 @@ int sfmhip_triangulate_dlt(const double* P, const int32_t* pair_of_obs,
                            const double* x0, const double* x1, int64_t n,
                            double* X4, void* stream);
 
+/* ---- S2b: robust N-view triangulation of tracks (build-defined) -------------
+ * S2 gives a track the point of the one pair it was first seen in.  This call estimates
+ * every track from all of its observations, some of which may be wrong matches, and
+ * reports the point, a status and the inlier set.  The reference has no counterpart.
+ * Restated in numpy by tests/tri_ref.py.  f64 arithmetic, one IEEE round-to-nearest
+ * step per operation in the order written, no FMA, correctly rounded / and sqrt; no
+ * floating-point atomics; every sum runs in the order of the sorted list, so two runs
+ * give the same bytes and nothing depends on the launch geometry.  All pointers are
+ * device memory unless marked host.
+ *
+ * Inputs.  poses [C][3][4] f64 world -> camera; cam [C][4] f64 = fx, fy, cx, cy; the
+ *   observations sorted by (track, camera) in the layout of sfmhip_ba_global*: pt_off
+ *   [N+1] i64, obs_cam [M] i32, pts2d [M][2] f64; a repeated (track, camera) pair is legal
+ *   and keeps the caller's order.  Track t has the L = pt_off[t+1] - pt_off[t]
+ *   observations at positions 0..L-1 of its segment.  A segment that is not inside
+ *   [0, M], is reversed or is longer than 2^20 is an empty track; an observation whose
+ *   camera is outside [0, C) is not an observation (never an inlier, residual NaN).
+ *   The segments must not overlap (pt_off non-decreasing, as the layout implies): every
+ *   track keeps its working set in its own range of `inlier`, so two tracks that share
+ *   observations read and write nothing out of bounds but leave an undefined result in
+ *   both.  track_order [N] i32 or NULL: the order in which the fit kernel's lanes take
+ *   the tracks (speed only: descending length keeps a wave's trip counts alike), a
+ *   permutation of 0..N-1; an entry outside [0, N) is skipped, a track that is not listed
+ *   keeps status 1, and a track listed twice is run by two lanes that share its working
+ *   set: undefined for that track like an overlap, in bounds all the same.
+ * Parameters.  reproj_px > 0 (thr2 = reproj_px reproj_px); cos_min in (0, 1], the cosine
+ *   of the smallest triangulation angle (c2 = cos_min cos_min); 1 <= max_hyp <= 2^20;
+ *   refine_iters >= 0.  The device uses no transcendentals.
+ * Per camera c_i = -((R[0][i] t0 + R[1][i] t1) + R[2][i] t2) is its centre.  For a point X
+ *   and an observation (u, v) of camera c with pose rows P0, P1, P2:
+ *     xc = ((P00 X0 + P01 X1) + P02 X2) + P03, yc and z likewise;  iz = 1 / z;
+ *     du = ((xc iz) fx + cx) - u;  dv = ((yc iz) fy + cy) - v;  e2 = du du + dv dv.
+ *   small(a, b, X), the angle at X between the rays to the centres of cameras a and b is
+ *   below the minimum:  ra = c_a - X, rb = c_b - X, d = (ra0 rb0 + ra1 rb1) + ra2 rb2,
+ *     n = |ra|^2 |rb|^2 (sums in that order);  small iff d > 0 and d d > c2 n.
+ * 1. Schedule.  The position pairs (a, b), a < b, in lexicographic order, n_pairs =
+ *   L (L - 1) / 2.  n_pairs <= max_hyp: hypothesis h is pair h; else there are max_hyp
+ *   hypotheses and hypothesis h is pair floor(h n_pairs / max_hyp) (i64).  A pair whose
+ *   observations share a camera, or have one outside [0, C), is skipped.
+ * 2. Model (closed form, not S2's DLT): the midpoint of the common perpendicular of the
+ *   two viewing rays.  x = (u - cx) / fx, y = (v - cy) / fy; the ray of observation a
+ *   leaves c_a along da_i = (R[0][i] x + R[1][i] y) + R[2][i]; w = c_a - c_b; with aa =
+ *   da.da, bb = da.db, cc = db.db, dd = da.w, ee = db.w (each (p0 q0 + p1 q1) + p2 q2):
+ *     den = aa cc - bb bb;  s = (bb ee - cc dd) / den;  t = (aa ee - bb dd) / den;
+ *     X_i = 0.5 ((c_a_i + s da_i) + (c_b_i + t db_i)).
+ *   Dropped if a coordinate of X is not finite, if small(a, b, X), or if observation a or
+ *   b is not in the set step 3 gives under X.
+ * 3. Classification under X.  Observation k is an inlier iff z > 0 and e2 <= thr2 (a NaN
+ *   fails; the pixel error is sqrt(e2), so this is error <= reproj_px).  The list is
+ *   sorted, so a camera's observations are consecutive: of a camera's inliers only the one
+ *   with the smallest e2 stays, the lowest position among equals.  count = the inliers
+ *   kept, cost = the sum of their e2 in list order.
+ * 4. Winner: the largest count, then the smallest cost, then the lowest h.
+ * 5. Fit to a set.  Start: the 4x4 normal matrix of the rows x P2 - P0, y P2 - P1 of the
+ *   set's observations (normalised coordinates, summed in list order), its null vector by
+ *   the fixed-sweep Jacobi of S2's code, X = y[0..2] / y[3].  Then exactly refine_iters
+ *   Gauss-Newton steps on (du, dv): J^T J (3x3) and J^T r summed in list order, the step
+ *   by cofactors, X -= step.  X1 is fitted to the winner's set; step 3 under X1 gives the
+ *   second set; fewer than two inliers there: status 4.  X2 is fitted to the second set,
+ *   which is the reported inlier set.
+ * 6. Final tests under X2: every coordinate finite, else 4; z > 0 for every inlier, else
+ *   4; some pair of inlier views that is not small(a, b, X2), else 3.
+ * Outputs.  X [N][3] f64 (NaN unless OK); status [N] i32: 0 OK, 1 fewer than two distinct
+ *   cameras, 2 no hypothesis survived, 3 final angle too small, 4 fit failed; n_inliers
+ *   [N] i32 and inlier [M] u8 (0 unless OK); residual [M] f64 = sqrt(e2) under X2 (NaN
+ *   where the track is not OK).  n_hyp (host, or NULL): the hypotheses scored.  phase_ms
+ *   (host [2], or NULL): when given, the call waits for its kernels and reports the
+ *   milliseconds of the scoring and of the select-and-fit kernel (tools only).
+ * Kernels: an initialisation (failure values, per-track hypothesis counts, centres), a
+ *   one-workgroup integer scan, then the scoring kernel over the flattened hypotheses of
+ *   all tracks (one lane per hypothesis, one record of count and cost each) and the
+ *   select-and-fit kernel (one lane per track, records scanned in h order).  The call
+ *   reads the hypothesis total back once, before the two phases, to size the records
+ *   (12 bytes each, from the scratch pool); nothing returns to the host between them.
+ * A null pointer or a negative size is SFMHIP_E_ARG, as are max_hyp < 1, refine_iters < 0
+ *   and a threshold that is not finite and positive; shapes are checked before the
+ *   empty-call no-op: with N = 0, M = 0 or C < 2 every status is 1 and no phase runs.   */
+int sfmhip_triangulate_tracks(const double* poses, const double* cam, int C, const int64_t* pt_off, int64_t N,
+                              const int32_t* obs_cam, const double* pts2d, int64_t M,
+                              const int32_t* track_order, double reproj_px, double cos_min, int max_hyp,
+                              int refine_iters, double* X /* [N][3] */, int32_t* status /* [N] */,
+                              int32_t* n_inliers /* [N] */, uint8_t* inlier /* [M] */, double* residual /* [M] */,
+                              int64_t* n_hyp /* host */, float* phase_ms /* host [2] */, void* stream);
+
 /* ---- S3/S5: reprojection residual + scipy 2-point grouped FD Jacobian ----
  * sfm.py:87-91 (residual via cv2.projectPoints, no distortion) and
  * least_squares(..., jac_sparsity=ba_sparse(...)) sfm.py:37-38.
